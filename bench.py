@@ -23,10 +23,14 @@ boxes (seeded random branching from the root) dealt round-robin
 over the N ranks (the root on rank 0; B per rank: weak scaling); later rounds
 pop their descendants, and every --lb-every rounds the ranks rebalance their
 open nodes by bound (dist.rebalance, inside the timed loop).
-Supplementary objects: the round-1/2 fixed batch (tls4-lin), complete trees
-from the root, configs 3/4/5, the glob batch.
+A plain run sets up, warms up, times the K steps and prints the line.
+--dump-outputs DIR also writes what the last timed round returned (below).
+--full adds everything else: the CPU baselines, config 2's complete trees
+and the supplementary objects (the round-1/2 fixed batch (tls4-lin),
+complete trees from the root, configs 3/4/5, the glob batch).
 
-Run: python bench.py [--gpus N --steps K --warmup W --batch B]
+Run: python bench.py [--gpus N --steps K --warmup W --batch B --full
+                      --dump-outputs DIR]
      N > 1: one process per GPU, either launched by torch.distributed.run or,
      without WORLD_SIZE in the environment, started by this script itself
      (launch_ranks); the round collectives are the engine's own (mgpu_comm_*
@@ -961,6 +965,7 @@ def tree_rounds(ctx, dev, rank, world, p, LB, UB, args):
             acc["rccl_ms"].append(ev[0].elapsed_time(ev[1]))
             acc["open"] = st.open
         state["prev"] = cur
+        state["last"] = st
         return most
 
     lb_pick = B if args.lb_pick == 'batch' else 0
@@ -1017,6 +1022,8 @@ def tree_rounds(ctx, dev, rank, world, p, LB, UB, args):
     if na[0] != 0:
         raise RuntimeError(f"headline: {int(na[0])} device allocation(s) ({int(na[1])} bytes, "
                            f"all ranks) inside the timed rounds")
+    if args.dump_outputs:
+        dump_outputs(ctx, rank, world, state["last"], args.dump_outputs)
     # after the timed rounds: the next nodes of this pool, with the parent
     # bases they carry, for the CPU baseline (exported and imported back)
     pool_sample = None
@@ -1029,6 +1036,50 @@ def tree_rounds(ctx, dev, rank, world, p, LB, UB, args):
     return {"elapsed": tot, "nodes": nodes, "lps": lps, "kernels": kernels,
             "summary": summary, "incumbent": state["inc"],
             "rccl_ms": float(np.sum(acc["rccl_ms"])), "pool_sample": pool_sample}
+
+
+STATS_FIELDS = ("rounds", "nodes", "ndec", "open", "last_batch", "incumbent", "pruned", "lps",
+                "pivots", "sb_lps", "sb_pivots", "sb_pruned", "sb_modified", "pfi_pivots")
+DUMP_MAX_BYTES = 48 << 20   # open_nodes' share of --dump-outputs' 64 MB, over all ranks
+
+
+def dump_outputs(ctx, rank, world, st, out_dir):
+    """--dump-outputs: what the caller of the last timed mgpu_bnb_round holds,
+    as float64 .npy files (rank r > 0 writes <name>.rank<r>.npy):
+
+      round_stats   the mgpu_bnb_stats the round returned, flattened in the
+                    order of STATS_FIELDS (ndec is five counts; the counts
+                    are cumulative since mgpu_bnb_init)
+      incumbent_x   the best integer-feasible point so far (mgpu_bnb_best),
+                    written once an incumbent exists
+      open_nodes    the pool the round left: the next open nodes, topmost
+                    first, as migration rows [k, mgpu_bnb_row_width] ([lb | ub
+                    | bound | depth | basis as a pivot path], bnb_migrate.hip);
+                    the whole pool or its top DUMP_MAX_BYTES / world
+
+    The boxes are seeded, so two runs with the same arguments write the same
+    arrays.  The rows leave the pool and are imported back (after the timed
+    rounds).  They are exported bottom row first, the order in which
+    mgpu_bnb_import_dev stacks them again (row t on top of row t - 1), so the
+    depth-first stack is left as it was: whatever runs next (--full's CPU
+    baseline sample) sees the same nodes with or without the dump."""
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = f".rank{rank}" if rank else ""
+
+    def save(name, a):
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), np.asarray(a, dtype=np.float64))
+    flat = []
+    for f in STATS_FIELDS:
+        v = getattr(st, f)
+        flat.extend(v if f == "ndec" else [v])
+    save("round_stats", flat)
+    inc, x = ctx.bnb_best()
+    if math.isfinite(inc):
+        save("incumbent_x", x)
+    lbs = ctx.bnb_pick(max(1, DUMP_MAX_BYTES // world // (8 * ctx.bnb_row_width())))
+    rows = ctx.bnb_export_rows(np.arange(len(lbs))[::-1])      # bottom row first
+    save("open_nodes", rows.cpu().numpy()[::-1])
+    ctx.bnb_import_rows(rows)
 
 
 def fixed_batch(ctx, dev, rank, world, args, reps=10):
@@ -1238,6 +1289,13 @@ def main():
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=20)
     ap.add_argument('--warmup', type=int, default=3)
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline also run the CPU baselines, config 2\'s complete '
+                         'trees and the supplementary objects (the --no-* options pick among '
+                         'them), and write --supp-out')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps write what the last step returned (round_stats, '
+                         'incumbent_x, open_nodes: see dump_outputs) as DIR/<name>.npy')
     ap.add_argument('--batch', type=int, default=524288,
                     help='open nodes per GPU per step (524288: K1 persistent waves refill '
                          'their lanes; 131072 = one node per resident lane)')
@@ -1247,7 +1305,7 @@ def main():
     ap.add_argument('--oa-tree-batch', type=int, default=16384,
                     help="open nodes per GPU per round of config 2's complete tree "
                          "(tls4_oa_tree in the line)")
-    ap.add_argument('--supp-out', default=os.path.join('gpurun_out', 'bench_supplementary.json'),
+    ap.add_argument('--supp-out', default='bench_supplementary.json',
                     help='where the supplementary objects (trees, configs 3/4/5, glob) are '
                          'written; the stdout line carries their headline numbers only')
     ap.add_argument('--oa-tree-eta-cap', type=int, default=48,
@@ -1286,6 +1344,10 @@ def main():
     ap.add_argument('--no-knapsack', action='store_true',
                     help='skip the supplementary config-3 batch (1000 knapsack nodes)')
     args = ap.parse_args()
+    if not args.full:
+        # a plain run measures the headline alone
+        for k in ('cpu_baseline', 'bnb', 'convex', 'qp', 'glob', 'fixed', 'oa_tree', 'knapsack'):
+            setattr(args, 'no_' + k, True)
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         # `python bench.py --gpus N`: this process only launches; N fresh rank
         # processes (one per GPU) run the bench and rank 0 prints the line.
@@ -1343,9 +1405,11 @@ def main():
                    f"{nodes / elapsed / 1e6:.2f} M nodes/s")
     TB = args.tree_batch
     oa_tree = {} if args.no_oa_tree else tls4_oa_tree(ctx, dev, rank, world, args)
-    progress(rank, f"tls4_oa_tree done: {oa_tree.get('nodes_per_s', 0.0) / 1e6:.2f} M nodes/s")
+    if oa_tree:
+        progress(rank, f"tls4_oa_tree done: {oa_tree['nodes_per_s'] / 1e6:.2f} M nodes/s")
     rel_tree = {} if args.no_oa_tree else tls4_oa_rel_tree(ctx, dev, rank, world, args)
-    progress(rank, f"tls4_oa_rel_tree done: {rel_tree}")
+    if rel_tree:
+        progress(rank, f"tls4_oa_rel_tree done: {rel_tree}")
     supp = {}
     for key, skip, fn in (
             ("fixed_batch", args.no_fixed, lambda: fixed_batch(ctx, dev, rank, world, args)),
@@ -1359,7 +1423,8 @@ def main():
             ("glob_batch", args.no_glob, lambda: glob_batch(ctx, dev, rank, world, args)),
             ("glob_tree", args.no_glob, lambda: glob_tree(ctx, dev, rank, world, args))):
         supp[key] = None if skip else fn()
-        progress(rank, f"{key} done")
+        if not skip:
+            progress(rank, f"{key} done")
 
     if rank == 0:
         kernels = h["kernels"]
@@ -1389,13 +1454,18 @@ def main():
         full.update(supp)
         supp_path = os.path.abspath(args.supp_out)
         try:
-            os.makedirs(os.path.dirname(supp_path), exist_ok=True)
-            with open(supp_path, 'w') as fh:
-                json.dump(full, fh, indent=1)
+            if args.full:
+                os.makedirs(os.path.dirname(supp_path), exist_ok=True)
+                with open(supp_path, 'w') as fh:
+                    json.dump(full, fh, indent=1)
         except OSError as e:
             supp_path = f"not written ({e})"
         line = compact_line(args, world, B, p, h, elapsed, nodes, lps, roofline, kernels, cpu,
                             oa_tree, supp, supp_path, rel_tree)
+        if not args.full:
+            # a plain run measured none of these
+            for k in ("cpu_baseline", "tls4_oa_tree", "tls4_oa_rel_tree", "supplementary"):
+                del line[k]
         if rehearse:
             line["rehearsal"] = "all ranks on device 0 over gloo (not a scaling number)"
         print(json.dumps(line), flush=True)

@@ -8,10 +8,10 @@ in their header lines is the pin:
                      4 nonlinear rows, 85 binaries, 4 nonlinear integers,
                      25 objective-gradient entries;
   nvs08.nl:2-8       3 vars, 3 rows (all nonlinear), 9 Jacobian nnz,
-                     1 nonlinear objective, 2 nonlinear integers;
-  color_lab2_4x0.nl  (binary "b" format) 300 vars, 61 rows, 360 nnz.
-tls4.nl and nvs08.nl are committed as data under tests/golden/nl/;
-color_lab2_4x0.nl (1.5 MB) is read from /root/reference when present.
+                     1 nonlinear objective, 2 nonlinear integers.
+tls4.nl and nvs08.nl are committed as data under tests/golden/nl/.  Both are
+text ("g") files; the binary ("b") reader is run on the same two models
+rewritten in the binary format by this module's own encoder.
 """
 import math
 import os
@@ -25,7 +25,6 @@ from minotaur_amd.problem import LinProblem, from_nl_linear, nvs08_oa
 HERE = os.path.dirname(os.path.abspath(__file__))
 NL = os.path.join(HERE, 'golden', 'nl')
 INST = os.path.join(HERE, '..', 'minotaur_amd', 'instances')
-COLOR = '/root/reference/test_instances/color_lab2_4x0.nl'
 
 
 def _nnz(m):
@@ -89,13 +88,99 @@ def test_nvs08_header_and_expressions():
     assert abs(f - ((x1 - 3) ** 2 + (x2 - 2) ** 2 + (x0 + 4) ** 2)) <= 1e-12
 
 
-@pytest.mark.skipif(not os.path.exists(COLOR), reason='color_lab2_4x0.nl needs /root/reference')
-def test_color_lab2_binary_format_header():
-    m = read_nl(COLOR)
-    assert (m.n, m.m, _nnz(m)) == (300, 61, 360)
-    assert int(np.sum(m.var_type == 0)) == 300
-    assert np.all(m.con_lb == m.con_ub) and not m.con_nonlinear.any()
-    assert m.obj_nonlinear
+def _write_binary(text_path, out_path):
+    """The text ("g") file at text_path rewritten segment by segment in the
+    binary ("b") format: the ten header lines stay text, every integer
+    becomes a little-endian int32 and every number a float64."""
+    import struct
+    from minotaur_amd.nl import _NARY_OPS, _UNARY_OPS
+    with open(text_path) as fh:
+        raw = fh.read().splitlines()
+    body = [ln.split('#', 1)[0].strip() for ln in raw[10:]]
+    n, m = (int(v) for v in raw[1].split()[:2])
+    out = bytearray(('b' + raw[0][1:] + '\n' + '\n'.join(raw[1:10]) + '\n').encode())
+    pos = [0]
+
+    def line():
+        pos[0] += 1
+        return body[pos[0] - 1]
+
+    def I(v):
+        out.extend(struct.pack('<i', int(v)))
+
+    def F(v):
+        out.extend(struct.pack('<d', float(v)))
+
+    def expr():
+        tok = line()
+        k, rest = tok[0], tok[1:]
+        out.extend(k.encode())
+        if k == 'n':
+            F(rest)
+        elif k == 'v':
+            I(rest)
+        else:
+            assert k == 'o', tok
+            op = int(rest)
+            I(op)
+            if op in _NARY_OPS:
+                cnt = int(line())
+                I(cnt)
+            else:
+                cnt = 3 if op in (35, 65) else 1 if op in _UNARY_OPS else 2
+            for _ in range(cnt):
+                expr()
+
+    while pos[0] < len(body):
+        ln = line()
+        if not ln:
+            continue
+        seg, rest = ln[0], ln[1:].split()
+        out.extend(seg.encode())
+        if seg == 'C':
+            I(rest[0])
+            expr()
+        elif seg == 'O':
+            I(rest[0])
+            I(rest[1])
+            expr()
+        elif seg in 'rb':
+            for _ in range(m if seg == 'r' else n):
+                p = line().split()
+                out.extend(p[0].encode())
+                for v in p[1:]:
+                    (I if p[0] == '5' else F)(v)     # code 5: two ints
+        elif seg == 'k':
+            I(rest[0])
+            for _ in range(int(rest[0])):
+                I(line())
+        else:
+            assert seg in 'xdJG', ln
+            if seg in 'JG':
+                I(rest[0])
+            I(rest[-1])
+            for _ in range(int(rest[-1])):
+                p = line().split()
+                I(p[0])
+                F(p[1])
+    with open(out_path, 'wb') as fh:
+        fh.write(out)
+
+
+@pytest.mark.parametrize('name', ['tls4', 'nvs08'])
+def test_binary_format_reads_as_the_text_format(name, tmp_path):
+    """The binary-format reader on the committed instances: each file
+    rewritten in the "b" format gives the model its text form gives."""
+    src = os.path.join(NL, name + '.nl')
+    _write_binary(src, tmp_path / 'b.nl')
+    a, b = read_nl(src), read_nl(str(tmp_path / 'b.nl'))
+    assert (a.name, a.n, a.m, a.obj_sense, a.obj_const, a.obj_nonlinear) == \
+        (b.name, b.n, b.m, b.obj_sense, b.obj_const, b.obj_nonlinear)
+    for k in ('var_lb', 'var_ub', 'var_type', 'con_lb', 'con_ub', 'con_nonlinear'):
+        assert np.array_equal(getattr(a, k), getattr(b, k)), k
+    assert a.rows == b.rows and a.obj_grad == b.obj_grad and _nnz(b) > 0
+    assert a.con_expr == b.con_expr and a.obj_expr == b.obj_expr
+    assert len(b.con_expr) == int(a.con_nonlinear.sum()) > 0
 
 
 def test_nvs08_oa_instance_and_validity():

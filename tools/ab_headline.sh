@@ -7,7 +7,7 @@
 set -o pipefail
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out/${TAG:-ab}; mkdir -p $O; cd $R; export TMPDIR=/tmp
-ARGS=${ARGS:---steps 10 --warmup 2 --no-cpu-baseline --no-bnb --no-qp --no-convex --no-knapsack --no-glob --no-fixed}
+ARGS=${ARGS:---full --steps 10 --warmup 2 --no-cpu-baseline --no-bnb --no-qp --no-convex --no-knapsack --no-glob --no-fixed}
 for rep in 1 2; do
 for v in ${VARIANTS:-base}; do
   # a variant is a library name, optionally followed by +VAR=value env settings
