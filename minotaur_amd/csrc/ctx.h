@@ -152,8 +152,6 @@ int fail(mgpu_ctx *c, int code, const char *fmt, ...) {
                   __LINE__);                                                     \
   } while (0)
 
-inline size_t al16h(size_t b) { return (b + 15) & ~(size_t)15; }
-
 template <class T>
 hipError_t upload(DevBuf &b, const T *src, size_t count) {
   hipError_t e = b.ensure(count * sizeof(T) > 0 ? count * sizeof(T) : 16);

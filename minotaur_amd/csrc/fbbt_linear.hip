@@ -26,6 +26,7 @@
 //  * Compiled with -ffp-contract=off: no fused multiply-add, as the
 //    reference's x86-64 build (no FMA without -march).
 #include "mgpu_internal.h"
+#include "wave.h"
 
 #include <type_traits>
 
@@ -35,37 +36,6 @@ namespace {
 // write-out order of the global variant: var-outer (each store one
 // coalesced 512-B row; the node-outer order measured the same)
 constexpr bool kFbbtOutVarOuter = true;
-
-// ---- wave-uniform broadcast ------------------------------------------------
-__device__ __forceinline__ int rl(int v, int k) { return __builtin_amdgcn_readlane(v, k); }
-__device__ __forceinline__ double rld(double v, int k) {
-  const long long b = __double_as_longlong(v);
-  const int lo = __builtin_amdgcn_readlane((int)(b & 0xffffffffLL), k);
-  const int hi = __builtin_amdgcn_readlane((int)(b >> 32), k);
-  return __longlong_as_double(((long long)hi << 32) | (unsigned)lo);
-}
-__device__ __forceinline__ uint64_t rlu64(uint64_t v, int k) {
-  const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(v & 0xffffffffu), k);
-  const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(v >> 32), k);
-  return ((uint64_t)hi << 32) | lo;
-}
-
-// v_readfirstlane: the value of the first ACTIVE lane, so it is correct
-// under any EXEC mask (v_readlane of a fixed lane is not: inside a
-// divergent region the compiler may copy or reload a VGPR for the active
-// lanes only, and a fixed lane may be inactive -- round 5 met exactly that)
-__device__ __forceinline__ int rfl(int v) { return __builtin_amdgcn_readfirstlane(v); }
-__device__ __forceinline__ double rfld(double v) {
-  const long long b = __double_as_longlong(v);
-  const int lo = __builtin_amdgcn_readfirstlane((int)(b & 0xffffffffLL));
-  const int hi = __builtin_amdgcn_readfirstlane((int)(b >> 32));
-  return __longlong_as_double(((long long)hi << 32) | (unsigned)lo);
-}
-__device__ __forceinline__ uint64_t rflu64(uint64_t v) {
-  const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(v & 0xffffffffu));
-  const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(v >> 32));
-  return ((uint64_t)hi << 32) | lo;
-}
 
 // Per-lane slice of a chunk of up to 64 term records (tightenInts_'s column
 // list, read with v_readlane in uniform control flow only).

@@ -23,9 +23,8 @@
 //    butterflies with deterministic lowest-index tie-breaks.
 //  * Pivots: B^{-1} row r is published to LDS once and read back as a
 //    broadcast for both the pivot row and the rank-1 update.
-#include "mgpu_internal.h"
+#include "lp_common.h"
 #include "sb_rule.h"
-#include "wave.h"
 
 namespace mgpu {
 
@@ -61,21 +60,8 @@ __device__ unsigned long long g_lp_stamps[16];
 
 namespace {
 
-constexpr double kPTol = 1e-7;    // primal feasibility (Clp default)
-constexpr double kDTol = 1e-7;    // dual feasibility (Clp default)
-constexpr double kPivTol = 1e-9;  // smallest |alpha_rq| allowed to pivot
-constexpr double kArt0 = 1e7;     // first artificial box half-width
-constexpr double kInfB = 1e30;    // |bound| >= this is infinite in the LP
-
-constexpr int kUnknownStatus = 12;  // EngineUnknownStatus: node not solved
-
-enum : int8_t { ST_LB = 0, ST_UB = 1, ST_FREE = 2, ST_BASIC = 3 };
-
-__host__ __device__ constexpr size_t al16(size_t b) { return (b + 15) & ~(size_t)15; }
-
 __host__ __device__ inline size_t shared_a_bytes(int n, int m, int nnz) {
-  return al16((size_t)(n + 1) * 4) + al16((size_t)nnz * 4) + al16((size_t)nnz * 8) +
-         al16((size_t)(m + 1) * 4) + al16((size_t)nnz * 4) + al16((size_t)nnz * 8) +
+  return lp_matrix_bytes(n, m, nnz) +
          3 * al16((size_t)n * 8) + 2 * al16((size_t)m * 8);  // c, box (batch 1), row bounds
 }
 // Shared warm start (one basis for every node, e.g. the root optimum)
@@ -94,106 +80,12 @@ __host__ __device__ inline size_t rows_wave_bytes(int m, int nnz) {
   return 2 * al16((size_t)nnz * 8) + 2 * al16((size_t)m * 8);
 }
 
-__device__ __forceinline__ double art_lo(double thi, double ab) {
-  return (thi < kInfB ? thi : 0.0) - ab;
-}
-__device__ __forceinline__ double art_hi(double tlo, double ab) {
-  return (tlo > -kInfB ? tlo : 0.0) + ab;
-}
-
-struct Ctx {
-  // shared matrix
-  const int *colptr, *rowidx, *rowptr, *ccol;
-  const double *cval, *rval;
-  // per-wave column state
+// the shared matrix, the problem, the wave's column state
+struct Ctx : LpMat, LpView {
   double *d, *z, *blo, *bhi, *al, *t2, *rho, *aq;
   int8_t *st, *art;
-  // problem
-  int n, m, N;
-  const double *nlb, *nub, *rlo, *rhi, *c;
-  int ocol;        // >= 0: objective is osign * x[ocol] (bound LP), else c
-  double osign;
   int lane;
-  __device__ __forceinline__ double cj(int j) const {
-    return ocol < 0 ? c[j] : (j == ocol ? osign : 0.0);
-  }
-  __device__ __forceinline__ double tlo(int j) const {
-    const double v = j < n ? nlb[j] : rlo[j - n];
-    return v < -kInfB ? -INFINITY : v;
-  }
-  __device__ __forceinline__ double thi(int j) const {
-    const double v = j < n ? nub[j] : rhi[j - n];
-    return v > kInfB ? INFINITY : v;
-  }
 };
-
-// rho' a_j over CSC column j in CSC order; four entries' loads are issued
-// before their products are summed (the adds keep the sequential order)
-__device__ __forceinline__ double col_dot(const Ctx &C, int j) {
-  double a = 0.0;
-  int t = C.colptr[j];
-  const int e = C.colptr[j + 1];
-  for (; t + 4 <= e; t += 4) {
-    const int i0 = C.rowidx[t], i1 = C.rowidx[t + 1], i2 = C.rowidx[t + 2], i3 = C.rowidx[t + 3];
-    const double v0 = C.cval[t], v1 = C.cval[t + 1], v2 = C.cval[t + 2], v3 = C.cval[t + 3];
-    const double r0 = C.rho[i0], r1 = C.rho[i1], r2 = C.rho[i2], r3 = C.rho[i3];
-    a += v0 * r0;
-    a += v1 * r1;
-    a += v2 * r2;
-    a += v3 * r3;
-  }
-  for (; t < e; ++t) a += C.cval[t] * C.rho[C.rowidx[t]];
-  return a;
-}
-
-// oracle place_nonbasic
-__device__ __forceinline__ void place_nonbasic(const Ctx &C, int j, double ab) {
-  const double lo = C.blo[j], hi = C.bhi[j], dj = C.d[j];
-  const bool lo_f = lo > -kInfB, hi_f = hi < kInfB;
-  if (lo_f && hi_f && lo == hi) {
-    C.st[j] = ST_LB;
-    C.z[j] = lo;
-    return;
-  }
-  if (dj > kDTol) {
-    if (!lo_f) {
-      C.blo[j] = art_lo(hi, ab);
-      C.art[j] |= 1;
-    }
-    C.st[j] = ST_LB;
-    C.z[j] = C.blo[j];
-  } else if (dj < -kDTol) {
-    if (!hi_f) {
-      C.bhi[j] = art_hi(lo, ab);
-      C.art[j] |= 2;
-    }
-    C.st[j] = ST_UB;
-    C.z[j] = C.bhi[j];
-  } else {
-    if (lo_f) {
-      C.st[j] = ST_LB;
-      C.z[j] = lo;
-    } else if (hi_f) {
-      C.st[j] = ST_UB;
-      C.z[j] = hi;
-    } else {
-      C.st[j] = ST_FREE;
-      C.z[j] = 0.0;
-    }
-  }
-}
-
-// oracle grow_art
-__device__ __forceinline__ void grow_art(const Ctx &C, double ab) {
-  for (int j = C.lane; j < C.N; j += 64) {
-    const int8_t a = C.art[j];
-    if (!a || C.st[j] == ST_BASIC) continue;
-    if (a & 1) C.blo[j] = art_lo(C.thi(j), ab);
-    if (a & 2) C.bhi[j] = art_hi(C.tlo(j), ab);
-    if (C.st[j] == ST_LB) C.z[j] = C.blo[j];
-    if (C.st[j] == ST_UB) C.z[j] = C.bhi[j];
-  }
-}
 
 // oracle compute_primals: z_B = -B^{-1} (N z_N); lane k forms w_k from CSR
 // row k in column order, then lane i takes row i of B^{-1} times w.
@@ -246,12 +138,8 @@ __global__ __launch_bounds__(64 * W) void lp_dual_kernel(DevLP lp, LpIO io) {
   const int lane0 = threadIdx.x & 63, wave = threadIdx.x >> 6;
   // node list (K3P overflow re-solve): a workgroup with no node of it
   // leaves before staging anything (uniform over the workgroup)
-  const int lo = io.node_list != nullptr ? io.list_lo : 0;
-  int nsolve = io.batch;
-  if (io.node_list != nullptr) {
-    nsolve = *io.node_count;
-    if (nsolve > io.list_hi) nsolve = io.list_hi;
-  }
+  int lo, nsolve;
+  node_range(io, lo, nsolve);
   // self-resetting node counter: every wave counts itself out, the last one
   // zeroes the counter for the next launch on the stream (no fill kernel)
   auto leave = [&]() {
@@ -268,20 +156,7 @@ __global__ __launch_bounds__(64 * W) void lp_dual_kernel(DevLP lp, LpIO io) {
 
   // ---- stage the constraint matrix (CSC + CSR) once per workgroup ----
   unsigned char *p = smem;
-  int *s_colptr = (int *)p;      p += al16((size_t)(n + 1) * 4);
-  int *s_rowidx = (int *)p;      p += al16((size_t)nnz * 4);
-  double *s_cval = (double *)p;  p += al16((size_t)nnz * 8);
-  int *s_rowptr = (int *)p;      p += al16((size_t)(m + 1) * 4);
-  int *s_ccol = (int *)p;        p += al16((size_t)nnz * 4);
-  double *s_rval = (double *)p;  p += al16((size_t)nnz * 8);
-  for (int t = threadIdx.x; t <= n; t += 64 * W) s_colptr[t] = lp.colptr[t];
-  for (int t = threadIdx.x; t <= m; t += 64 * W) s_rowptr[t] = lp.rowptr[t];
-  for (int t = threadIdx.x; t < nnz; t += 64 * W) {
-    s_rowidx[t] = lp.rowidx[t];
-    s_cval[t] = lp.cval[t];
-    s_ccol[t] = lp.ccol[t];
-    s_rval[t] = lp.rval[t];
-  }
+  const LpMat A = stage_matrix<64 * W>(p, lp);
   // objective and row bounds beside the matrix (the objective sum and the
   // rebuilt reduced costs read them column by column); a single-LP launch
   // (HipLPEngine's route) also stages its box here, so its loads overlap
@@ -373,9 +248,8 @@ __global__ __launch_bounds__(64 * W) void lp_dual_kernel(DevLP lp, LpIO io) {
     unsigned char *wp =
         p + (size_t)wave * (wave_bytes(N) + (nrows ? rows_wave_bytes(m, nnz) : 0));
     Ctx C;
-    C.colptr = s_colptr; C.rowidx = s_rowidx; C.cval = s_cval;
-    C.rowptr = s_rowptr; C.ccol = s_ccol; C.rval = s_rval;
-    C.d = (double *)wp;   wp += al16((size_t)N * 8);
+    static_cast<LpMat &>(C) = A;
+    C.d = (double *)wp;  wp += al16((size_t)N * 8);
     C.z = (double *)wp;   wp += al16((size_t)N * 8);
     C.blo = (double *)wp; wp += al16((size_t)N * 8);
     C.bhi = (double *)wp; wp += al16((size_t)N * 8);
@@ -394,25 +268,28 @@ __global__ __launch_bounds__(64 * W) void lp_dual_kernel(DevLP lp, LpIO io) {
     C.lane = lane;
 
     if (io.skip != nullptr && io.skip[b] != 0) {  // pruned by FBBT: not solved
-      if (lane == 0) {
-        io.status[b] = kUnknownStatus;
-        io.obj[b] = INFINITY;
-        io.iters[b] = 0;
-      }
+      if (lane == 0) write_unsolved(io, b, kUnknownStatus);
       note(kUnknownStatus, INFINITY);
       held = false;
       continue;
     }
     if (nrows) {
       // the node's matrix and row bounds: the loaded values, then its own
-      // entries (OsiLPEngine::changeConstraint of the rewritten rows)
+      // entries (OsiLPEngine::changeConstraint of the rewritten rows).
+      // K3 keeps three per-node phases written out that K3L takes from
+      // lp_common.h: this one (node_rows_overlay), the working bounds
+      // (working_bounds) and the placement loop (place_columns) below.  As
+      // calls, the glob batch's LP step (per-node rows) measured 0.46 %
+      // slower than the written-out text, 4.507 against 4.487 ms; with this
+      // phase alone written out still 4.505 against 4.490, with all three
+      // 4.491 against 4.490.  A change to one is made in lp_common.h too.
       double *wc = (double *)wp;  wp += al16((size_t)nnz * 8);
       double *wr = (double *)wp;  wp += al16((size_t)nnz * 8);
       double *wlo = (double *)wp; wp += al16((size_t)m * 8);
       double *whi = (double *)wp;
       for (int t = lane; t < nnz; t += 64) {
-        wc[t] = s_cval[t];
-        wr[t] = s_rval[t];
+        wc[t] = A.cval[t];
+        wr[t] = A.rval[t];
       }
       for (int i = lane; i < m; i += 64) {
         wlo[i] = s_rlo[i];
@@ -439,6 +316,7 @@ __global__ __launch_bounds__(64 * W) void lp_dual_kernel(DevLP lp, LpIO io) {
     }
 
     // ---- working bounds; an empty box is infeasible before any pivot ----
+    // (lp_common.h's working_bounds, written out: see the per-node rows above)
     bool bad = false;
     for (int j = lane; j < N; j += 64) {
       C.blo[j] = C.tlo(j);
@@ -532,6 +410,7 @@ __global__ __launch_bounds__(64 * W) void lp_dual_kernel(DevLP lp, LpIO io) {
     wave_sync();
     STAMP(12);
     double art_bound = kArt0;
+    // (lp_common.h's place_columns, written out: see the per-node rows above)
     for (int j = lane; j < N; j += 64) {
       if (C.st[j] == ST_BASIC) continue;
       const double lo = C.blo[j], hi = C.bhi[j], dj = C.d[j];
@@ -601,7 +480,7 @@ __global__ __launch_bounds__(64 * W) void lp_dual_kernel(DevLP lp, LpIO io) {
           break;
         }
         art_bound *= 1e3;
-        grow_art(C, art_bound);
+        grow_art(C, art_bound, lane, 64);
         zB = compute_primals(C, binv);
         fresh = true;
         continue;
@@ -643,7 +522,7 @@ __global__ __launch_bounds__(64 * W) void lp_dual_kernel(DevLP lp, LpIO io) {
           if (j >= n) {
             a = -C.rho[j - n];
           } else {
-            a = col_dot(C, j);
+            a = col_dot(C, C.rho, j);
           }
           // Harris ratios without divergent branches: one numerator pair and
           // denominator per case, two divisions for every lane (the same
@@ -673,7 +552,7 @@ __global__ __launch_bounds__(64 * W) void lp_dual_kernel(DevLP lp, LpIO io) {
           break;
         }
         art_bound *= 1e3;
-        grow_art(C, art_bound);
+        grow_art(C, art_bound, lane, 64);
         zB = compute_primals(C, binv);
         fresh = true;
         continue;

@@ -31,22 +31,10 @@
 //  * Reductions (pricing arg-max, ratio min, pass-2 arg-max) are DPP wave
 //    reductions combined across the 4 waves through LDS, with the oracle's
 //    lowest-index tie-breaks.
-#include "mgpu_internal.h"
-#include "wave.h"
+#include "lp_common.h"
 
 namespace mgpu {
 namespace {
-
-constexpr double kPTol = 1e-7;    // primal feasibility (Clp default)
-constexpr double kDTol = 1e-7;    // dual feasibility (Clp default)
-constexpr double kPivTol = 1e-9;  // smallest |alpha_rq| allowed to pivot
-constexpr double kArt0 = 1e7;     // first artificial box half-width
-constexpr double kInfB = 1e30;    // |bound| >= this is infinite in the LP
-constexpr int kUnknownStatus = 12;
-
-enum : int8_t { ST_LB = 0, ST_UB = 1, ST_FREE = 2, ST_BASIC = 3 };
-
-__host__ __device__ constexpr size_t al16(size_t b) { return (b + 15) & ~(size_t)15; }
 
 __host__ __device__ inline size_t large_lds_bytes(int n, int m) {
   const size_t N = (size_t)n + m;
@@ -55,27 +43,11 @@ __host__ __device__ inline size_t large_lds_bytes(int n, int m) {
 }
 
 template <int kT>  // threads per workgroup = one node
-struct S {
+struct S : LpMat, LpView {   // the matrix in HBM (L2-resident)
   double *d, *z, *blo, *bhi, *al, *t2, *rho, *aq, *w, *redv;
   int8_t *st, *art;
   int *head, *redi;
   double *Bi;                   // HBM, column-major: (i, k) at k * m + i
-  const int *colptr, *rowidx, *rowptr, *ccol;
-  const double *cval, *rval;
-  const double *nlb, *nub, *rlo, *rhi, *c;
-  int n, m, N, ocol;
-  double osign;
-  __device__ __forceinline__ double cj(int j) const {
-    return ocol < 0 ? c[j] : (j == ocol ? osign : 0.0);
-  }
-  __device__ __forceinline__ double tlo(int j) const {
-    const double v = j < n ? nlb[j] : rlo[j - n];
-    return v < -kInfB ? -INFINITY : v;
-  }
-  __device__ __forceinline__ double thi(int j) const {
-    const double v = j < n ? nub[j] : rhi[j - n];
-    return v > kInfB ? INFINITY : v;
-  }
 };
 
 // ---- workgroup reductions (every thread calls them) ------------------------
@@ -120,63 +92,15 @@ __device__ __forceinline__ void blk_argmax(double &v, int &i, const S<kT> &s) {
   for (int w = 1; w < kT / 64; ++w) amax_combine(v, i, s.redv[w], s.redi[w]);
 }
 
-// oracle col_dot: v' a_j over CSC column j in CSC order (v in LDS)
+// oracle col_dot: v' a_j over CSC column j, logicals included, in CSC order
+// (v in LDS; the matrix comes from L2, so a plain loop, not lp_common.h's
+// four-in-flight col_dot)
 template <int kT>
-__device__ __forceinline__ double col_dot(const S<kT> &s, const double *v, int j) {
+__device__ __forceinline__ double col_dot_seq(const S<kT> &s, const double *v, int j) {
   if (j >= s.n) return -v[j - s.n];
   double a = 0.0;
   for (int t = s.colptr[j]; t < s.colptr[j + 1]; ++t) a += s.cval[t] * v[s.rowidx[t]];
   return a;
-}
-
-// oracle place_nonbasic
-template <int kT>
-__device__ __forceinline__ void place_nonbasic(const S<kT> &s, int j, double ab) {
-  const double lo = s.blo[j], hi = s.bhi[j], dj = s.d[j];
-  const bool lo_f = lo > -kInfB, hi_f = hi < kInfB;
-  if (lo_f && hi_f && lo == hi) {
-    s.st[j] = ST_LB;
-    s.z[j] = lo;
-    return;
-  }
-  if (dj > kDTol) {
-    if (!lo_f) {
-      s.blo[j] = (hi < kInfB ? hi : 0.0) - ab;
-      s.art[j] |= 1;
-    }
-    s.st[j] = ST_LB;
-    s.z[j] = s.blo[j];
-  } else if (dj < -kDTol) {
-    if (!hi_f) {
-      s.bhi[j] = (lo > -kInfB ? lo : 0.0) + ab;
-      s.art[j] |= 2;
-    }
-    s.st[j] = ST_UB;
-    s.z[j] = s.bhi[j];
-  } else if (lo_f) {
-    s.st[j] = ST_LB;
-    s.z[j] = lo;
-  } else if (hi_f) {
-    s.st[j] = ST_UB;
-    s.z[j] = hi;
-  } else {
-    s.st[j] = ST_FREE;
-    s.z[j] = 0.0;
-  }
-}
-
-// oracle grow_art
-template <int kT>
-__device__ __forceinline__ void grow_art(const S<kT> &s, double ab) {
-  for (int j = threadIdx.x; j < s.N; j += kT) {
-    const int8_t a = s.art[j];
-    if (!a || s.st[j] == ST_BASIC) continue;
-    const double tl = s.tlo(j), th = s.thi(j);
-    if (a & 1) s.blo[j] = (th < kInfB ? th : 0.0) - ab;
-    if (a & 2) s.bhi[j] = (tl > -kInfB ? tl : 0.0) + ab;
-    if (s.st[j] == ST_LB) s.z[j] = s.blo[j];
-    if (s.st[j] == ST_UB) s.z[j] = s.bhi[j];
-  }
 }
 
 // oracle compute_primals: w = N z_N per row (CSR row k in column order, the
@@ -356,20 +280,15 @@ __global__ __launch_bounds__(kT) void lp_large_kernel(DevLP lp, LpIO io, double 
     s.redi = (int *)p;
   }
   s.Bi = binv_slots + (size_t)blockIdx.x * m * m;
-  s.colptr = lp.colptr; s.rowidx = lp.rowidx; s.cval = lp.cval;
-  s.rowptr = lp.rowptr; s.ccol = lp.ccol; s.rval = lp.rval;
+  const LpMat A0{lp.colptr, lp.rowidx, lp.rowptr, lp.ccol, lp.cval, lp.rval};  // as loaded
+  static_cast<LpMat &>(s) = A0;
   s.rlo = lp.rlo; s.rhi = lp.rhi; s.c = lp.objd;
   s.n = n; s.m = m; s.N = N;
   const size_t mm = (size_t)m * m;
 
-  // node list (the product-form kernels' overflow re-solve, as K3's):
-  // positions list_lo .. min(*node_count, list_hi) of node_list
-  const int lo = io.node_list != nullptr ? io.list_lo : 0;
-  int nsolve = io.batch;
-  if (io.node_list != nullptr) {
-    nsolve = *io.node_count;
-    if (nsolve > io.list_hi) nsolve = io.list_hi;
-  }
+  // node list (the product-form kernels' overflow re-solve, as K3's)
+  int lo, nsolve;
+  node_range(io, lo, nsolve);
   // nodes from a device counter when the host gives one (dynamic schedule:
   // a workgroup that finishes early takes the next node), else a static stride
   __shared__ int s_next;
@@ -391,62 +310,22 @@ __global__ __launch_bounds__(kT) void lp_large_kernel(DevLP lp, LpIO io, double 
     s.osign = io.obj_col != nullptr ? io.obj_sign[b] : 0.0;
 
     if (io.skip != nullptr && io.skip[b] != 0) {  // pruned by FBBT: not solved
-      if (tid == 0) {
-        io.status[b] = kUnknownStatus;
-        io.obj[b] = INFINITY;
-        io.iters[b] = 0;
-      }
+      if (tid == 0) write_unsolved(io, b, kUnknownStatus);
       continue;
     }
     const bool nrows = io.nr.vals != nullptr;
     double *wg = nrows ? io.nr.wg + (size_t)blockIdx.x * io.nr.wg_stride : nullptr;
     if (nrows) {
-      // the node's matrix and row bounds (K3's per-node rows): the loaded
-      // values, then its own entries (OsiLPEngine::changeConstraint of the
-      // rewritten rows), in this workgroup's HBM slot
+      // the node's matrix and row bounds (K3's per-node rows), in this
+      // workgroup's HBM slot
       const int nnz = lp.nnz;
       double *wc = wg, *wr = wc + nnz, *wlo = wr + nnz, *whi = wlo + m;
-      for (int t = tid; t < nnz; t += kT) {
-        wc[t] = lp.cval[t];
-        wr[t] = lp.rval[t];
-      }
-      for (int i = tid; i < m; i += kT) {
-        wlo[i] = lp.rlo[i];
-        whi[i] = lp.rhi[i];
-      }
-      __syncthreads();
-      const double *rec = io.nr.vals + (size_t)b * io.nr.stride;
-      for (int q = tid; q < io.nr.ncoef; q += kT) {
-        double v = rec[io.nr.coef_src[q]];
-        if (fabs(v) <= kLfTol) v = 0.0;
-        wc[io.nr.csc_pos[q]] = v;
-        wr[io.nr.csr_pos[q]] = v;
-      }
-      for (int q = tid; q < io.nr.nrow; q += kT) {
-        const int r = io.nr.row[q];
-        if (io.nr.lo_src[q] >= 0) wlo[r] = rec[io.nr.lo_src[q]];
-        if (io.nr.hi_src[q] >= 0) whi[r] = rec[io.nr.hi_src[q]];
-      }
-      __syncthreads();
-      s.cval = wc;
-      s.rval = wr;
-      s.rlo = wlo;
-      s.rhi = whi;
+      node_rows_overlay(s, s, A0, lp.rlo, lp.rhi, io.nr, b, nnz, wc, wr, wlo, whi, tid, kT,
+                        [] { __syncthreads(); });
     }
     // ---- working bounds; an empty box is infeasible before any pivot ----
-    bool bad = false;
-    for (int j = tid; j < N; j += kT) {
-      s.blo[j] = s.tlo(j);
-      s.bhi[j] = s.thi(j);
-      s.art[j] = 0;
-      bad |= s.blo[j] > s.bhi[j] + kPTol;
-    }
-    if (blk_any(bad, s)) {
-      if (tid == 0) {
-        io.status[b] = 2;
-        io.obj[b] = INFINITY;
-        io.iters[b] = 0;
-      }
+    if (blk_any(working_bounds(s, tid, kT), s)) {
+      if (tid == 0) write_unsolved(io, b, 2);
       continue;
     }
 
@@ -492,7 +371,7 @@ __global__ __launch_bounds__(kT) void lp_large_kernel(DevLP lp, LpIO io, double 
         }
         __syncthreads();
         for (int j = tid; j < N; j += kT)
-          s.d[j] = s.st[j] == ST_BASIC ? 0.0 : (j < n ? s.c[j] : 0.0) - col_dot(s, s.rho, j);
+          s.d[j] = s.st[j] == ST_BASIC ? 0.0 : (j < n ? s.c[j] : 0.0) - col_dot_seq(s, s.rho, j);
       } else {
         // bound LP (oracle compute_duals): y = c_B' B^-1 = osign * row r of
         // B^-1 when ocol is basic in row r, else 0; d_j = c_j - y' a_j
@@ -505,7 +384,7 @@ __global__ __launch_bounds__(kT) void lp_large_kernel(DevLP lp, LpIO io, double 
           s.rho[k] = rr != INT_MAX ? 0.0 + s.osign * s.Bi[(size_t)k * m + rr] : 0.0;
         __syncthreads();
         for (int j = tid; j < N; j += kT)
-          s.d[j] = s.st[j] == ST_BASIC ? 0.0 : s.cj(j) - col_dot(s, s.rho, j);
+          s.d[j] = s.st[j] == ST_BASIC ? 0.0 : s.cj(j) - col_dot_seq(s, s.rho, j);
       }
     } else {
       for (int i = tid; i < m; i += kT) s.head[i] = n + i;
@@ -518,26 +397,7 @@ __global__ __launch_bounds__(kT) void lp_large_kernel(DevLP lp, LpIO io, double 
     }
     __syncthreads();
     double art_bound = kArt0;
-    for (int j = tid; j < N; j += kT) {
-      if (s.st[j] == ST_BASIC) continue;
-      const double lo = s.blo[j], hi = s.bhi[j], dj = s.d[j];
-      bool keep = false;
-      if (warm) {
-        const int8_t v = s.st[j];
-        if (v == ST_LB && lo > -kInfB && dj >= -kDTol) {
-          s.z[j] = lo;
-          keep = true;
-        } else if (v == ST_UB && hi < kInfB && dj <= kDTol) {
-          s.z[j] = hi;
-          keep = true;
-        } else if (lo == hi && lo > -kInfB) {
-          s.st[j] = ST_LB;
-          s.z[j] = lo;
-          keep = true;
-        }
-      }
-      if (!keep) place_nonbasic(s, j, art_bound);
-    }
+    place_columns(s, warm, art_bound, tid, kT);
     compute_primals(s);
 
     int status = kUnknownStatus, iters = 0;
@@ -592,7 +452,7 @@ __global__ __launch_bounds__(kT) void lp_large_kernel(DevLP lp, LpIO io, double 
           break;
         }
         art_bound *= 1e3;
-        grow_art(s, art_bound);
+        grow_art(s, art_bound, tid, kT);
         compute_primals(s);
         fresh = true;
         continue;
@@ -618,7 +478,7 @@ __global__ __launch_bounds__(kT) void lp_large_kernel(DevLP lp, LpIO io, double 
         const int8_t v = s.st[j];
         double a = 0.0, t2 = INFINITY;
         if (v != ST_BASIC && s.blo[j] != s.bhi[j]) {
-          a = col_dot(s, s.rho, j);
+          a = col_dot_seq(s, s.rho, j);
           const double at = sigma * a, dj = s.d[j];
           if (v == ST_LB && at > kPivTol) {
             const double t = (fmax(dj, 0.0) + kDTol) / at;
@@ -646,7 +506,7 @@ __global__ __launch_bounds__(kT) void lp_large_kernel(DevLP lp, LpIO io, double 
           break;
         }
         art_bound *= 1e3;
-        grow_art(s, art_bound);
+        grow_art(s, art_bound, tid, kT);
         compute_primals(s);
         fresh = true;
         continue;

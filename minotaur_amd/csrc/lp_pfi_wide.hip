@@ -30,46 +30,24 @@
 //  * Column state (reduced cost, pivot-row entry, Harris ratio, status bits)
 //    in VGPRs for column j = s*64 + lane (n + m <= 64*S), values and working
 //    bounds in a per-wave LDS slice, as in K3P.
-#include "mgpu_internal.h"
-#include "wave.h"
+#include "lp_pfi_cols.h"
 
 namespace mgpu {
 namespace {
 
-constexpr double kPTol = 1e-7;
-constexpr double kDTol = 1e-7;
-constexpr double kPivTol = 1e-9;
-constexpr double kArt0 = 1e7;
-constexpr double kInfB = 1e30;
-constexpr int kUnknownStatus = 12;
 constexpr int kR = 2;            // basis rows per lane
 constexpr int kKE = kPfiWideMax; // eta file
 constexpr int kWaves = 8;        // waves per workgroup (2 per SIMD)
 
 static_assert(kKE < 64, "K3PW never reaches the dense 64-pivot primal refresh");
 
-enum : int { ST_LB = 0, ST_UB = 1, ST_FREE = 2, ST_BASIC = 3 };
-constexpr int kArtLo = 4, kArtHi = 8, kFixed = 16;
-
-__host__ __device__ constexpr size_t al16(size_t b) { return (b + 15) & ~(size_t)15; }
-
+// matrix (CSC + CSR), B0^{-1}, warm-start d / status / head
 __host__ __device__ inline size_t pfiw_shared_bytes(int n, int m, int nnz) {
-  const int N = n + m;
-  return al16((size_t)(n + 1) * 4) + al16((size_t)nnz * 4) + al16((size_t)nnz * 8) +
-         al16((size_t)(m + 1) * 4) + al16((size_t)nnz * 4) + al16((size_t)nnz * 8) +
-         al16((size_t)m * (m + 1) * 8) + al16((size_t)N * 8) + al16((size_t)N * 4) +
-         al16((size_t)m * 4);
+  return lp_matrix_bytes(n, m, nnz) + pfi_warm_bytes(n, m);
 }
 // per wave: rho [128] + column values, lower and upper working bounds [N]
 __host__ __device__ inline size_t pfiw_wave_bytes(int N) {
   return 64 * kR * 8 + 3 * al16((size_t)N * 8);
-}
-
-__device__ __forceinline__ double art_lo(double thi, double ab) {
-  return (thi < kInfB ? thi : 0.0) - ab;
-}
-__device__ __forceinline__ double art_hi(double tlo, double ab) {
-  return (tlo > -kInfB ? tlo : 0.0) + ab;
 }
 
 // row p's value of a per-row register pair (p wave-uniform)
@@ -80,43 +58,7 @@ __device__ __forceinline__ int rrowi(const int (&v)[kR], int p) {
   return rl(p < 64 ? v[0] : v[1], p & 63);
 }
 
-struct Prob {
-  const int *colptr, *rowidx, *rowptr, *ccol;
-  const double *cval, *rval;
-  const double *b0;  // (B0^{-1})_{ik} = b0[k*ld + i]
-  int n, m, N, ld;
-  const double *nlb, *nub, *rlo, *rhi, *c;
-  int ocol;
-  double osign;
-  __device__ __forceinline__ double cj(int j) const {
-    return ocol < 0 ? c[j] : (j == ocol ? osign : 0.0);
-  }
-  __device__ __forceinline__ double tlo(int j) const {
-    const double v = j < n ? nlb[j] : rlo[j - n];
-    return v < -kInfB ? -INFINITY : v;
-  }
-  __device__ __forceinline__ double thi(int j) const {
-    const double v = j < n ? nub[j] : rhi[j - n];
-    return v > kInfB ? INFINITY : v;
-  }
-  // rho' a_j over CSC column j (four loads in flight, adds in CSC order)
-  __device__ __forceinline__ double col_dot(const double *rho, int j) const {
-    double a = 0.0;
-    int t = colptr[j];
-    const int e = colptr[j + 1];
-    for (; t + 4 <= e; t += 4) {
-      const int i0 = rowidx[t], i1 = rowidx[t + 1], i2 = rowidx[t + 2], i3 = rowidx[t + 3];
-      const double v0 = cval[t], v1 = cval[t + 1], v2 = cval[t + 2], v3 = cval[t + 3];
-      const double r0 = rho[i0], r1 = rho[i1], r2 = rho[i2], r3 = rho[i3];
-      a += v0 * r0;
-      a += v1 * r1;
-      a += v2 * r2;
-      a += v3 * r3;
-    }
-    for (; t < e; ++t) a += cval[t] * rho[rowidx[t]];
-    return a;
-  }
-};
+using Prob = PfiProb;
 
 // v <- E_{k-1} ... E_0 v (oracle pfi_apply_etas): out_p' = eta_p out_p,
 // out_i' = out_i + eta_i out_p; rows >= m hold 0 in v and in every eta
@@ -139,47 +81,22 @@ __device__ __forceinline__ void apply_etas(double (&v)[kR], const double (&eta)[
 template <int S>
 __global__ __launch_bounds__(64 * kWaves) void lp_pfiw_kernel(DevLP lp, LpIO io, PfiIO px) {
   extern __shared__ __align__(16) unsigned char smem[];
-  const int n = lp.n, m = lp.m, N = n + m, nnz = lp.nnz, ld = m + 1;
+  const int n = lp.n, m = lp.m, N = n + m, ld = m + 1;
   const int lane0 = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int kmax = px.kmax;
 
   // ---- stage the matrix, B0^{-1} and the warm start once per workgroup ----
-  unsigned char *p = smem;
-  int *s_colptr = (int *)p;      p += al16((size_t)(n + 1) * 4);
-  int *s_rowidx = (int *)p;      p += al16((size_t)nnz * 4);
-  double *s_cval = (double *)p;  p += al16((size_t)nnz * 8);
-  int *s_rowptr = (int *)p;      p += al16((size_t)(m + 1) * 4);
-  int *s_ccol = (int *)p;        p += al16((size_t)nnz * 4);
-  double *s_rval = (double *)p;  p += al16((size_t)nnz * 8);
-  double *s_b0 = (double *)p;    p += al16((size_t)m * ld * 8);
-  double *s_wd = (double *)p;    p += al16((size_t)N * 8);
-  int *s_wst = (int *)p;         p += al16((size_t)N * 4);
-  int *s_whead = (int *)p;       p += al16((size_t)m * 4);
   constexpr int T = 64 * kWaves;
-  for (int t = threadIdx.x; t <= n; t += T) s_colptr[t] = lp.colptr[t];
-  for (int t = threadIdx.x; t <= m; t += T) s_rowptr[t] = lp.rowptr[t];
-  for (int t = threadIdx.x; t < nnz; t += T) {
-    s_rowidx[t] = lp.rowidx[t];
-    s_cval[t] = lp.cval[t];
-    s_ccol[t] = lp.ccol[t];
-    s_rval[t] = lp.rval[t];
-  }
-  for (int t = threadIdx.x; t < m * m; t += T)  // ABI: column-major, t = k*m + i
-    s_b0[(t / m) * ld + t % m] = io.ws.binv[t];
-  for (int t = threadIdx.x; t < N; t += T) {
-    s_wd[t] = io.ws.d != nullptr ? io.ws.d[t] : 0.0;  // bound LPs rebuild d
-    const int8_t s = io.ws.st[t];
-    s_wst[t] = s == ST_BASIC ? ST_LB : s;
-  }
-  for (int t = threadIdx.x; t < m; t += T) s_whead[t] = io.ws.head[t];
-  __syncthreads();
-  for (int t = threadIdx.x; t < m; t += T) s_wst[s_whead[t]] = ST_BASIC;  // basic = in head
-  __syncthreads();
+  unsigned char *p = smem;
+  const LpMat A = stage_matrix<T>(p, lp);
+  const PfiWarm W = pfi_stage_warm<T>(p, io.ws, n, m);
+  double *s_wd = W.wd;
+  int *s_wst = W.wst, *s_whead = W.whead;
+  pfi_mark_basic<T>(W, m);
 
   Prob P;
-  P.colptr = s_colptr; P.rowidx = s_rowidx; P.cval = s_cval;
-  P.rowptr = s_rowptr; P.ccol = s_ccol; P.rval = s_rval;
-  P.b0 = s_b0;
+  static_cast<LpMat &>(P) = A;
+  P.b0 = W.b0;
   P.n = n; P.m = m; P.N = N; P.ld = ld;
   P.rlo = lp.rlo; P.rhi = lp.rhi; P.c = lp.objd;
   double *rho = (double *)(p + (size_t)wave * pfiw_wave_bytes(N));
@@ -203,37 +120,15 @@ __global__ __launch_bounds__(64 * kWaves) void lp_pfiw_kernel(DevLP lp, LpIO io,
     P.osign = io.obj_col != nullptr ? io.obj_sign[b] : 0.0;
 
     if (io.skip != nullptr && io.skip[b] != 0) {
-      if (lane == 0) {
-        io.status[b] = kUnknownStatus;
-        io.obj[b] = INFINITY;
-        io.iters[b] = 0;
-      }
+      if (lane == 0) write_unsolved(io, b, kUnknownStatus);
       continue;
     }
 
     // ---- working bounds; an empty box is infeasible before any pivot ----
     double tl[S], th[S];
     int sa[S];
-    bool bad = false;
-#pragma unroll
-    for (int s = 0; s < S; ++s) {
-      const int j = s * 64 + lane;
-      const bool valid = j < N;
-      tl[s] = valid ? P.tlo(j) : 0.0;
-      th[s] = valid ? P.thi(j) : 0.0;
-      sa[s] = valid ? s_wst[j] : ST_BASIC;  // slots past N act as basic: never touched
-      bad |= valid && tl[s] > th[s] + kPTol;
-      if (valid) {
-        lo[j] = tl[s];
-        hi[j] = th[s];
-      }
-    }
-    if (__any(bad)) {
-      if (lane == 0) {
-        io.status[b] = 2;
-        io.obj[b] = INFINITY;
-        io.iters[b] = 0;
-      }
+    if (pfi_working_bounds(P, [&](int j) { return s_wst[j]; }, lo, hi, lane, tl, th, sa)) {
+      if (lane == 0) write_unsolved(io, b, 2);
       continue;
     }
     wave_sync();
@@ -277,62 +172,14 @@ __global__ __launch_bounds__(64 * kWaves) void lp_pfiw_kernel(DevLP lp, LpIO io,
         const int j = s * 64 + lane;
         d[s] = 0.0;
         if (j < N && sa[s] != ST_BASIC)
-          d[s] = P.cj(j) - (j >= n ? -rho[j - n] : P.col_dot(rho, j));
+          d[s] = P.cj(j) - (j >= n ? -rho[j - n] : col_dot(P, rho, j));
       }
       wave_sync();
     }
 
     // ---- nonbasic placement: keep the warm status when dual feasible ----
     double art_bound = kArt0;
-#pragma unroll
-    for (int s = 0; s < S; ++s) {
-      const int j = s * 64 + lane;
-      if (j >= N) continue;
-      if (sa[s] == ST_BASIC) {  // the fixed bit matters once it leaves the basis
-        zc[j] = 0.0;
-        sa[s] = ST_BASIC | (tl[s] == th[s] ? kFixed : 0);
-        continue;
-      }
-      double lo_j = tl[s], hi_j = th[s], z;
-      const double dj = d[s];
-      const bool lo_f = lo_j > -kInfB, hi_f = hi_j < kInfB;
-      int st = sa[s], art = 0;
-      if (st == ST_LB && lo_f && dj >= -kDTol) {
-        z = lo_j;
-      } else if (st == ST_UB && hi_f && dj <= kDTol) {
-        z = hi_j;
-      } else if (lo_j == hi_j && lo_f) {
-        st = ST_LB;
-        z = lo_j;
-      } else if (dj > kDTol) {  // oracle place_nonbasic
-        if (!lo_f) {
-          lo_j = art_lo(hi_j, art_bound);
-          lo[j] = lo_j;
-          art = kArtLo;
-        }
-        st = ST_LB;
-        z = lo_j;
-      } else if (dj < -kDTol) {
-        if (!hi_f) {
-          hi_j = art_hi(lo_j, art_bound);
-          hi[j] = hi_j;
-          art = kArtHi;
-        }
-        st = ST_UB;
-        z = hi_j;
-      } else if (lo_f) {
-        st = ST_LB;
-        z = lo_j;
-      } else if (hi_f) {
-        st = ST_UB;
-        z = hi_j;
-      } else {
-        st = ST_FREE;
-        z = 0.0;
-      }
-      zc[j] = z;
-      sa[s] = st | art | (lo_j == hi_j ? kFixed : 0);
-    }
+    pfi_place(P, sa, d, tl, th, zc, lo, hi, lane, art_bound);
 
     double eta[kKE][kR];
 #pragma unroll
@@ -393,21 +240,6 @@ __global__ __launch_bounds__(64 * kWaves) void lp_pfiw_kernel(DevLP lp, LpIO io,
 #pragma unroll
       for (int rs = 0; rs < kR; ++rs) zB[rs] = -zB[rs];
     };
-    // oracle grow_art
-    auto grow = [&](double ab) {
-#pragma unroll
-      for (int s = 0; s < S; ++s) {
-        const int j = s * 64 + lane;
-        const int st = sa[s] & 3;
-        if (!(sa[s] & (kArtLo | kArtHi)) || st == ST_BASIC) continue;
-        double lo_j = lo[j], hi_j = hi[j];
-        if (sa[s] & kArtLo) lo_j = lo[j] = art_lo(P.thi(j), ab);
-        if (sa[s] & kArtHi) hi_j = hi[j] = art_hi(P.tlo(j), ab);
-        if (st == ST_LB) zc[j] = lo_j;
-        if (st == ST_UB) zc[j] = hi_j;
-        sa[s] = (sa[s] & ~kFixed) | (lo_j == hi_j ? kFixed : 0);
-      }
-    };
 
     primals();
     int status = kUnknownStatus;
@@ -432,15 +264,7 @@ __global__ __launch_bounds__(64 * kWaves) void lp_pfiw_kernel(DevLP lp, LpIO io,
       asm volatile("" : "+v"(best));
       if (best == 0.0) {
         // optimal on the maintained primal values (K3P's rule, oracle pfi mode)
-        bool g = false;
-#pragma unroll
-        for (int s = 0; s < S; ++s) {
-          const int st = sa[s] & 3;
-          if (st != ST_BASIC && (((st == ST_LB) && (sa[s] & kArtLo)) ||
-                                 ((st == ST_UB) && (sa[s] & kArtHi))))
-            g = true;
-        }
-        if (!__any(g)) {
+        if (!pfi_needs_growth(sa)) {
           status = 0;
           break;
         }
@@ -449,7 +273,7 @@ __global__ __launch_bounds__(64 * kWaves) void lp_pfiw_kernel(DevLP lp, LpIO io,
           break;
         }
         art_bound *= 1e3;
-        grow(art_bound);
+        pfi_grow(P, sa, zc, lo, hi, lane, art_bound);
         primals();
         continue;
       }
@@ -533,68 +357,26 @@ __global__ __launch_bounds__(64 * kWaves) void lp_pfiw_kernel(DevLP lp, LpIO io,
 
       // ---- pivot row and Harris pass 1 (pass-2 ratio kept per slot) ----
       double al[S], t2[S];
-      double tmax = INFINITY;
-#pragma unroll
-      for (int s = 0; s < S; ++s) {
-        const int j = s * 64 + lane;
-        double a = 0.0, tt = INFINITY;
-        const int st = sa[s] & 3;
-        if (st != ST_BASIC && !(sa[s] & kFixed)) {
-          a = j >= n ? -rho[j - n] : P.col_dot(rho, j);
-          const double at = sigma * a, dj = d[s], fat = fabs(at);
-          const bool lb = st == ST_LB && at > kPivTol, ub = st == ST_UB && at < -kPivTol,
-                     fr = st == ST_FREE && fat > kPivTol;
-          const double n2 = lb ? fmax(dj, 0.0) : ub ? fmin(dj, 0.0) : 0.0;
-          const double n1 = lb ? n2 + kDTol : ub ? n2 - kDTol : kDTol;
-          const double den = fr ? fat : at;
-          if (lb || ub || fr) {
-            const double tr = n1 / den;
-            tt = fr ? 0.0 : n2 / den;
-            if (tr < tmax) tmax = tr;
-          }
-        }
-        al[s] = a;
-        t2[s] = tt;
-      }
-      tmax = wave_min_dpp(tmax);
+      double tmax = wave_min_dpp(pfi_harris1(P, rho, sigma, sa, d, al, t2, lane));
       asm volatile("" : "+v"(tmax));
       if (tmax == INFINITY) {  // dual unbounded
-        bool boxed = false;
-#pragma unroll
-        for (int s = 0; s < S; ++s)
-          boxed |= (sa[s] & 3) != ST_BASIC && (sa[s] & (kArtLo | kArtHi)) != 0;
-        if (!__any(boxed) || art_bound >= 1e13) {
+        if (!pfi_any_boxed(sa) || art_bound >= 1e13) {
           status = 2;
           break;
         }
         art_bound *= 1e3;
-        grow(art_bound);
+        pfi_grow(P, sa, zc, lo, hi, lane, art_bound);
         primals();
         continue;
       }
-      // ---- Harris pass 2: largest |alpha| among ratios <= tmax; the owner
-      // lane keeps its candidate's reduced cost, alpha and status bits ----
-      double qa = 0.0, cd = 0.0, cal = 0.0;
-      int q = INT_MAX, csa = 0;
-#pragma unroll
-      for (int s = 0; s < S; ++s) {
-        if (t2[s] <= tmax) {
-          const double fa = fabs(al[s]);
-          if (fa > qa) {
-            qa = fa;
-            q = s * 64 + lane;
-            cd = d[s];
-            cal = al[s];
-            csa = sa[s];
-          }
-        }
-      }
-      wave_argmax_idx(qa, q);
+      // ---- Harris pass 2: largest |alpha| among ratios <= tmax ----
+      double qa, cd, cal;
+      int q, csa;
+      pfi_harris2(sa, d, al, t2, tmax, lane, qa, q, cd, cal, csa);
       if (qa == 0.0) {
         status = 2;
         break;
       }
-      const int ql = q & 63, qs = q >> 6;
 
       // ---- FTRAN: alpha_q = E...E B0^{-1} a_q ----
       double alq[kR];
@@ -628,40 +410,11 @@ __global__ __launch_bounds__(64 * kWaves) void lp_pfiw_kernel(DevLP lp, LpIO io,
       const double arq = rrow(alq, r);
 
       // ---- steps ----
-      double theta_d = rld(cd, ql) / rld(cal, ql);
-      if (sigma * theta_d < 0) theta_d = 0.0;
       const double theta_p = delta / arq;
       const int pl = rrowi(h, r);
-      const int pls = pl >> 6, pll = pl & 63;
-#pragma unroll
-      for (int s = 0; s < S; ++s)
-        if ((sa[s] & 3) != ST_BASIC) d[s] -= theta_d * al[s];
-      const double zq = zc[q] + theta_p;
-      const bool art_q = (rl(csa, ql) & (kArtLo | kArtHi)) != 0;
-      double bloq = lo[q], bhiq = hi[q];
-      const double bound_p = delta < 0 ? lo[pl] : hi[pl];
-      wave_sync();
-      if (art_q) {  // basic columns keep their true (infinite) bounds
-        bloq = P.tlo(q);
-        bhiq = P.thi(q);
-      }
-      if (lane == 0) {
-        zc[q] = 0.0;        // basic now (its value is zB of row r)
-        zc[pl] = bound_p;   // leaving column to its violated bound
-        lo[q] = bloq;
-        hi[q] = bhiq;
-      }
-#pragma unroll
-      for (int s = 0; s < S; ++s) {
-        if (s == qs && lane == ql) {
-          d[s] = 0.0;
-          sa[s] = ST_BASIC | (bloq == bhiq ? kFixed : 0);
-        }
-        if (s == pls && lane == pll) {
-          d[s] = -theta_d;
-          sa[s] = (delta < 0 ? ST_LB : ST_UB) | (sa[s] & kFixed);
-        }
-      }
+      double zq, bloq, bhiq;
+      pfi_pivot_cols(P, sa, d, al, zc, lo, hi, lane, q, pl, cd, cal, csa, sigma, delta, theta_p,
+                     zq, bloq, bhiq);
       const double inv = 1.0 / arq;
 #pragma unroll
       for (int rs = 0; rs < kR; ++rs) {
@@ -698,14 +451,7 @@ __global__ __launch_bounds__(64 * kWaves) void lp_pfiw_kernel(DevLP lp, LpIO io,
           const int i = rs * 64 + lane;
           if (i < m) px.c_head[(size_t)slot * m + i] = h[rs];
         }
-#pragma unroll
-        for (int s = 0; s < S; ++s) {
-          const int j = s * 64 + lane;
-          if (j < N) {
-            px.c_st[(size_t)slot * N + j] = (int8_t)(sa[s] & 3);
-            px.c_d[(size_t)slot * N + j] = d[s];
-          }
-        }
+        pfi_write_cont(px, slot, N, sa, d, lane);
         double *cb = px.c_binv + (size_t)slot * m * m;
         for (int c = 0; c < m; ++c) {
           double v[kR];

@@ -28,16 +28,12 @@
 // no consumer distinguishes.  The pivot row is broadcast through LDS.  Steps
 // whose column has no other nonzero (slack columns) skip the elimination with
 // a wave-uniform branch.
-#include "mgpu_internal.h"
-#include "wave.h"
+#include "lp_common.h"
 
 namespace mgpu {
 namespace {
 
 constexpr double kSingTol = 1e-12;  // oracle invert_basis: |pivot| < 1e-12 = singular
-enum : int8_t { ST_LB = 0, ST_UB = 1, ST_FREE = 2, ST_BASIC = 3 };
-
-__host__ __device__ constexpr size_t al16r(size_t b) { return (b + 15) & ~(size_t)15; }
 
 template <int M>
 __global__ __launch_bounds__(64) void lp_refactor_kernel(DevLP lp, RefacIO io) {
@@ -48,12 +44,12 @@ __global__ __launch_bounds__(64) void lp_refactor_kernel(DevLP lp, RefacIO io) {
   if (io.skip != nullptr && io.skip[b] != 0) return;  // K3 skips the node too
 
   unsigned char *p = smem;
-  double *wc = (double *)p;   p += al16r((size_t)nnz * 8);      // node CSC values
-  double *Ls = (double *)p;   p += al16r((size_t)m * ld * 8);   // dense B, then B^-1 rows
-  double *prow = (double *)p; p += al16r((size_t)2 * M * 8);    // pivot row broadcast
-  int32_t *pord = (int32_t *)p; p += al16r((size_t)M * 4);       // row pivoted at step k
-  double *y = (double *)p;    p += al16r((size_t)m * 8);
-  int32_t *hd = (int32_t *)p; p += al16r((size_t)m * 4);
+  double *wc = (double *)p;   p += al16((size_t)nnz * 8);      // node CSC values
+  double *Ls = (double *)p;   p += al16((size_t)m * ld * 8);   // dense B, then B^-1 rows
+  double *prow = (double *)p; p += al16((size_t)2 * M * 8);    // pivot row broadcast
+  int32_t *pord = (int32_t *)p; p += al16((size_t)M * 4);       // row pivoted at step k
+  double *y = (double *)p;    p += al16((size_t)m * 8);
+  int32_t *hd = (int32_t *)p; p += al16((size_t)m * 4);
   int8_t *st = (int8_t *)p;
 
   // the node's matrix: the loaded values, then its own entries
@@ -267,9 +263,9 @@ __global__ __launch_bounds__(64) void lp_refactor_kernel(DevLP lp, RefacIO io) {
 
 template <int M>
 size_t refactor_lds(int n, int m, int nnz) {
-  return al16r((size_t)nnz * 8) + al16r((size_t)m * (m + 1) * 8) + al16r((size_t)2 * M * 8) +
-         al16r((size_t)M * 4) + al16r((size_t)m * 8) + al16r((size_t)m * 4) +
-         al16r((size_t)(n + m));
+  return al16((size_t)nnz * 8) + al16((size_t)m * (m + 1) * 8) + al16((size_t)2 * M * 8) +
+         al16((size_t)M * 4) + al16((size_t)m * 8) + al16((size_t)m * 4) +
+         al16((size_t)(n + m));
 }
 
 template <int M>

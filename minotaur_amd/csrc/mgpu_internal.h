@@ -12,6 +12,9 @@ constexpr double kIntTol = 1e-6;
 constexpr double kETol = 1e-8;
 constexpr double kInfty = 1e20;
 
+// 16-byte rounding of every LDS / workspace carve-up, host and device
+__host__ __device__ constexpr size_t al16(size_t b) { return (b + 15) & ~(size_t)15; }
+
 // Reference VariableType numerics (Types.h:83-89).
 constexpr int kBinary = 0;
 constexpr int kInteger = 1;

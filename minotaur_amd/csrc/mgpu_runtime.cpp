@@ -499,7 +499,7 @@ int mgpu_fbbt(mgpu_ctx *c, int batch, const double *lb_in, const double *ub_in,
     // from and writes its results to a pinned host block, no copy-engine
     // transfers (as mgpu_lp_solve1)
     const size_t o_ub = nb, o_lo = 2 * nb, o_uo = 3 * nb, o_i = 4 * nb, o_mv = o_i + 16,
-                 o_ml = o_mv + al16h((size_t)cap * 4), o_mval = o_ml + al16h((size_t)cap * 4),
+                 o_ml = o_mv + al16((size_t)cap * 4), o_mval = o_ml + al16((size_t)cap * 4),
                  bytes = o_mval + (size_t)cap * 8 + 16;
     if (c->fb1_pin_bytes < bytes) {
       if (c->fb1_pin) (void)hipHostFree(c->fb1_pin);
@@ -651,8 +651,8 @@ int launch_lp(mgpu_ctx *c, const LpIO &io, const char *who) {
     if (io.path.k != nullptr && (wide || kcap > kPfiBig))
       return fail(c, MGPU_ERR_ARG, "%s: path warm starts run on K3P (m <= 64) with an eta cap "
                   "<= %d", who, kPfiBig);
-    const size_t sb_head = al16h((size_t)cap * m * 4), sb_st = al16h((size_t)cap * N),
-                 sb_d = al16h((size_t)cap * N * 8), sb_binv = al16h((size_t)cap * m * m * 8),
+    const size_t sb_head = al16((size_t)cap * m * 4), sb_st = al16((size_t)cap * N),
+                 sb_d = al16((size_t)cap * N * 8), sb_binv = al16((size_t)cap * m * m * 8),
                  sb_it = (size_t)cap * 4;
     HIPCHK(c, c->pfi_cont.ensure(sb_head + sb_st + sb_d + sb_binv + sb_it));
     // [0] overflow count, [1] K3P's next node, [2]/[3] the K3 follow-ups'
@@ -851,9 +851,9 @@ struct WsLayout {
 WsLayout ws_layout(int n, int m) {
   const size_t N = (size_t)n + m;
   WsLayout L;
-  L.st = al16h((size_t)m * 4);
-  L.d = L.st + al16h(N);
-  L.binv = L.d + al16h(N * 8);
+  L.st = al16((size_t)m * 4);
+  L.d = L.st + al16(N);
+  L.binv = L.d + al16(N * 8);
   L.bytes = (L.binv + (size_t)m * m * 8 + 255) & ~(size_t)255;
   return L;
 }
@@ -1238,12 +1238,12 @@ int mgpu_lp_solve_path(mgpu_ctx *c, int batch, const double *lb, const double *u
   hipStream_t s = c->stream;
   DevBuf buf;  // per-call workspace
   const size_t o_lb = 0, o_ub = o_lb + B * n * 8, o_wh = o_ub + B * n * 8,
-               o_wst = o_wh + al16h((size_t)m * 4), o_wd = o_wst + al16h((size_t)N),
+               o_wst = o_wh + al16((size_t)m * 4), o_wd = o_wst + al16((size_t)N),
                o_wb = o_wd + (size_t)N * 8, o_k = o_wb + (size_t)m * m * 8,
-               o_p = o_k + al16h(B * 4), o_st = o_p + B * P * 4, o_ost = o_st + al16h(B * N),
-               o_ok = o_ost + al16h(B * N), o_op = o_ok + al16h(B * 4),
-               o_stt = o_op + B * P * 4, o_obj = o_stt + al16h(B * 4),
-               o_it = o_obj + B * 8, o_x = o_it + al16h(B * 4), total = o_x + B * n * 8;
+               o_p = o_k + al16(B * 4), o_st = o_p + B * P * 4, o_ost = o_st + al16(B * N),
+               o_ok = o_ost + al16(B * N), o_op = o_ok + al16(B * 4),
+               o_stt = o_op + B * P * 4, o_obj = o_stt + al16(B * 4),
+               o_it = o_obj + B * 8, o_x = o_it + al16(B * 4), total = o_x + B * n * 8;
   HIPCHK(c, buf.ensure(total));
   char *d = buf.as<char>();
   auto h2d = [&](size_t off, const void *src, size_t bytes) {

@@ -187,7 +187,7 @@ int lp_solve_rows_wo(mgpu_ctx *c, int batch, const double *lb, const double *ub,
   if (ws_head) {
     // K3R: every node's warm start for its own matrix
     const size_t B = (size_t)batch;
-    const size_t s_head = al16h(B * m * 4), s_st = al16h(B * N), s_d = al16h(B * N * 8),
+    const size_t s_head = al16(B * m * 4), s_st = al16(B * N), s_d = al16(B * N * 8),
                  s_binv = B * m * m * 8;
     HIPCHK(c, c->nr_ws.ensure(s_head + s_st + s_d + s_binv));
     char *w = c->nr_ws.as<char>();
@@ -280,8 +280,8 @@ int mgpu_lp_refactor(mgpu_ctx *c, const int32_t *head, const int8_t *st, int32_t
   if (m > kLpMaxM || m == 0 || lp_refactor_lds_bytes(n, m, c->lp.nnz) > 160 * 1024)
     return fail(c, MGPU_ERR_ARG, "mgpu_lp_refactor: needs 0 < m <= %d (m=%d)", kLpMaxM, m);
   HIPCHK(c, hipSetDevice(c->device));
-  const size_t s_h = al16h((size_t)m * 4), s_s = al16h((size_t)N), s_d = al16h((size_t)N * 8),
-               s_b = al16h((size_t)m * m * 8);
+  const size_t s_h = al16((size_t)m * 4), s_s = al16((size_t)N), s_d = al16((size_t)N * 8),
+               s_b = al16((size_t)m * m * 8);
   // in: head, st; out: head, st, d, binv, singular flag
   HIPCHK(c, c->nr_vals.ensure(2 * s_h + 2 * s_s + s_d + s_b + 16));
   char *w = c->nr_vals.as<char>();

@@ -24,6 +24,23 @@ __device__ __forceinline__ uint64_t rlu64(uint64_t v, int k) {
   return ((uint64_t)hi << 32) | lo;
 }
 
+// v_readfirstlane: the value of the first ACTIVE lane, so it is correct
+// under any EXEC mask (v_readlane of a fixed lane is not: inside a
+// divergent region the compiler may copy or reload a VGPR for the active
+// lanes only, and a fixed lane may be inactive -- round 5 met exactly that)
+__device__ __forceinline__ int rfl(int v) { return __builtin_amdgcn_readfirstlane(v); }
+__device__ __forceinline__ double rfld(double v) {
+  const long long b = __double_as_longlong(v);
+  const int lo = __builtin_amdgcn_readfirstlane((int)(b & 0xffffffffLL));
+  const int hi = __builtin_amdgcn_readfirstlane((int)(b >> 32));
+  return __longlong_as_double(((long long)hi << 32) | (unsigned)lo);
+}
+__device__ __forceinline__ uint64_t rflu64(uint64_t v) {
+  const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(v & 0xffffffffu));
+  const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(v >> 32));
+  return ((uint64_t)hi << 32) | lo;
+}
+
 // Orders this wave's LDS writes before its later LDS reads by other lanes.
 __device__ __forceinline__ void wave_sync() {
   __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");

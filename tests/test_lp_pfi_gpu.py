@@ -163,18 +163,33 @@ def test_k3p_skip_and_empty_box(ctx):
     assert full.status[5] == 2 and full.iters[5] == 0
 
 
+def _slot_problem(ctx, kind, n, m, seed):
+    p = (random_mkp(seed, n, m) if kind == 'mkp'
+         else random_problem(seed, n=n, m=m, density=min(0.15, 4.0 / m)))
+    assert p.n + p.m <= 256 and p.m <= 64
+    ctx.load(p)
+    return p
+
+
 @pytest.mark.parametrize('kind,n,m,seed', [('mkp', 6, 16, 3), ('mkp', 40, 8, 1),
                                            ('mkp', 120, 8, 2), ('rand', 200, 40, 1),
                                            ('rand', 60, 60, 4)])
 def test_k3p_column_slot_counts(ctx, kind, n, m, seed):
     """S = ceil((n + m) / 64) from 1 to 4 column slots per lane."""
-    p = (random_mkp(seed, n, m) if kind == 'mkp'
-         else random_problem(seed, n=n, m=m, density=min(0.15, 4.0 / m)))
-    assert p.n + p.m <= 256 and p.m <= 64
-    ctx.load(p)
+    p = _slot_problem(ctx, kind, n, m, seed)
     LB, UB = random_boxes(p, 777, seed)
     _check(ctx, p, LB, UB, KCAP, want_x=True)
     _check(ctx, p, LB, UB, 5)
+
+
+@pytest.mark.parametrize('kind,n,m,seed', [('mkp', 6, 16, 3), ('rand', 60, 60, 4),
+                                           ('rand', 200, 40, 1)])
+def test_k3p_48_eta_build_column_slot_counts(ctx, kind, n, m, seed):
+    """The 48-eta build (caps above 32) at S = 1, 2 and 4 column slots per
+    lane; config 2's deep boxes above run it at S = 3."""
+    p = _slot_problem(ctx, kind, n, m, seed)
+    LB, UB = random_boxes(p, 300, seed)
+    _check(ctx, p, LB, UB, LP_PFI_BIG, want_x=True)
 
 
 def test_k3p_bound_lps_vs_oracle(ctx):

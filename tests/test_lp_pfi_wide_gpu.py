@@ -17,7 +17,7 @@ import numpy as np
 import pytest
 
 import oracle
-from minotaur_amd.problem import knapsack_oa, random_boxes
+from minotaur_amd.problem import knapsack_oa, random_boxes, random_problem
 from minotaur_amd.runtime import LP_PFI_WIDE_MAX as WCAP
 
 pytestmark = pytest.mark.gpu
@@ -95,6 +95,17 @@ def test_k3pw_node_boxes_vs_oracle(ctx, f, kmax):
     for b in np.nonzero(r.status == 0)[0][:24]:
         hs, ho = oracle.highs(p, LB[b], UB[b])
         assert hs == 0 and abs(ho - r.obj[b]) <= 1e-6 * max(1.0, abs(ho))
+
+
+def test_k3pw_four_column_slots_vs_oracle(ctx):
+    """S = 4 column slots per lane (193 <= n + m <= 256): the knapsack OA
+    shapes above give S = 2 and 3 only.  The smallest shape that selects it
+    (m = 65, n = 128); most of its LPs overflow into K3L."""
+    p = random_problem(1, n=128, m=65, density=min(0.15, 4.0 / 65))
+    assert 64 < p.m <= 128 and (p.n + p.m + 63) // 64 == 4
+    ctx.load(p)
+    LB, UB = random_boxes(p, 300, 1)
+    _check(ctx, p, LB, UB, WCAP, want_x=True)
 
 
 def test_k3pw_iteration_limit(ctx):
