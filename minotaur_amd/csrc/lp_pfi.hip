@@ -34,6 +34,7 @@
 // Arithmetic: oracle/lp_dual.c in product-form mode (dual_simplex_impl with
 // pfi > 0: pfi_btran, ftran_col, pfi_apply_etas, compute_primals), loop for
 // loop, so the GPU follows the oracle pivot for pivot (tests/test_lp_pfi_gpu.py).
+#include <cstddef>
 #include <type_traits>
 
 #include "lp_pfi_cols.h"
@@ -43,7 +44,12 @@ namespace mgpu {
 #ifdef MGPU_STAMPS
 // Diagnostic build only (-DMGPU_STAMPS, tools/lp_stamps.py --pfi): s_memtime
 // cycles per section summed over all waves; never compiled into the product.
-__device__ unsigned long long g_pfi_stamps[16];
+// [16 + 2 site + z]: eta steps of the forward passes per call site (0 primal
+// recompute, 1 FTRAN, 2 continuation inverse, 3 path replay), z = 1 those
+// whose pivot component v_p is zero (the step changes nothing).
+__device__ unsigned long long g_pfi_stamps[24];
+#define PCOUNT_ETA(site, vp) \
+  if (lane == 0) atomicAdd(&g_pfi_stamps[16 + 2 * (site) + ((vp) == 0.0 ? 1 : 0)], 1ull)
 #define PSTAMP_DECL unsigned long long st_acc[12] = {0}, st_t = __builtin_amdgcn_s_memtime();
 #define PSTAMP(i)                                             \
   do {                                                        \
@@ -60,6 +66,9 @@ __device__ unsigned long long g_pfi_stamps[16];
   do {            \
   } while (0)
 #define PSTAMP_FLUSH
+#define PCOUNT_ETA(site, vp) \
+  do {                       \
+  } while (0)
 #endif
 
 namespace {
@@ -100,15 +109,20 @@ using Prob = PfiProb;
 // the pivot row of eta t is lane t of prow
 template <int K>
 __device__ __forceinline__ double apply_etas(double v, const double (&eta)[K], int prow,
-                                             int k, int lane) {
+                                             int k, int lane, int site = 0) {
+  (void)site;   // the stamped build's call-site counters
 #pragma unroll
   for (int t = 0; t < K; ++t) {
     if (t < k) {
-      // select, not a (wave-uniform) branch: consecutive etas overlap
+      // select, not a (wave-uniform) branch: consecutive etas overlap.  On
+      // the headline v_p is zero in only ~20 % of the steps (stamped build's
+      // counters), and the branch measured 0.5 % slower with twice the
+      // spilled VGPRs
       const int p = rl(prow, t);
       const double vp = rld(v, p);
       const double nv = lane == p ? eta[t] * vp : v + eta[t] * vp;
       v = vp != 0.0 ? nv : v;
+      PCOUNT_ETA(site, vp);
     }
   }
   return v;
@@ -128,6 +142,7 @@ __device__ __forceinline__ void apply_etas_n(double (&v)[G], const double (&eta)
         const double vp = rld(v[i], p);
         const double nv = lane == p ? eta[t] * vp : v[i] + eta[t] * vp;
         v[i] = vp != 0.0 ? nv : v[i];
+        PCOUNT_ETA(3, vp);
       }
     }
   }
@@ -202,9 +217,17 @@ __global__ __launch_bounds__(256) void pfi_t0_kernel(DevLP lp, const double *bin
 template <int K>
 __device__ __forceinline__ double btran_etas(double u, const double (&eta)[K], int prow, int k,
                                              int lane) {
+  // k is wave uniform, but the compiler sees it as divergent (it changes
+  // under the pivot loop's laundered exit tests): a scalar copy makes each
+  // guard below an s_cmp and a branch instead of v_cmp + s_and_saveexec, and
+  // the compiler keeps far fewer scalars spilled across the chain (headline
+  // K3P 11.3 -> 10.9 ms).  The same copy in apply_etas
+  // doubles the 32-eta build's spilled VGPRs, so that pass keeps its vector
+  // guards.
+  const int ks = rfl(k);
 #pragma unroll
   for (int t = K - 1; t >= 0; --t) {
-    if (t < k) {
+    if (t < ks) {
       // all products zero and u_p zero: the sum would write a zero back;
       // skipping changes at most the sign of a zero, which no later step
       // reads (sums, and u_b0 skips zeros).  A nonzero u_p whose product
@@ -245,9 +268,35 @@ __device__ __forceinline__ double u_b0(const Prob &P, double u, int lane) {
   return rk;
 }
 
+// The kernel's arguments as one struct, so that a field's place in the
+// kernarg segment is its offsetof.
+struct PfiArgs {
+  DevLP lp;
+  LpIO io;
+  PfiIO px;
+};
+
+// A member of PfiArgs read from the kernarg segment at the point of use
+// (scalar loads of constant memory) instead of as a kernel parameter.  The
+// fields of a by-value parameter are all loaded at the kernel's entry and
+// stay live to their last use: the output pointers, the overflow and
+// continuation state and the decision's arguments, read only after a solve,
+// took ~100 scalar registers through the pivot loop, where they were spilled
+// to VGPR lanes and reloaded around every use (v_readlane / v_writelane: VALU
+// issue).  The empty asm keeps the loads below it.
+template <typename T>
+__device__ __forceinline__ const T &karg(size_t off) {
+  auto *p =
+      (const __attribute__((address_space(4))) char *)__builtin_amdgcn_kernarg_segment_ptr() + off;
+  asm volatile("" : "+s"(p));
+  return *(const T *)p;
+}
+
 template <int S, int K>
-__global__ __launch_bounds__((64 * waves_for<S, K>())) void lp_pfi_kernel(DevLP lp, LpIO io,
-                                                                       PfiIO px) {
+__global__ __launch_bounds__((64 * waves_for<S, K>())) void lp_pfi_kernel(PfiArgs args) {
+  const DevLP &lp = args.lp;
+  const LpIO &io = args.io;      // prologue and pivot loop; the outputs go through karg()
+  const PfiIO &px = args.px;
   constexpr int kWaves = waves_for<S, K>();
   extern __shared__ __align__(16) unsigned char smem[];
   const int n = lp.n, m = lp.m, N = n + m, ld = m + 1;
@@ -334,6 +383,8 @@ __global__ __launch_bounds__((64 * waves_for<S, K>())) void lp_pfi_kernel(DevLP 
 
     if (io.skip != nullptr && io.skip[b] != 0) {
       if (lane == 0) {
+        const LpIO &io = karg<LpIO>(offsetof(PfiArgs, io));
+        const PfiIO &px = karg<PfiIO>(offsetof(PfiArgs, px));
         write_unsolved(io, b, kUnknownStatus);
         if (io.path.k_out != nullptr) io.path.k_out[b] = 0;
         if (px.decide) {   // presolveNode found it infeasible (node_decide: 1)
@@ -378,6 +429,8 @@ __global__ __launch_bounds__((64 * waves_for<S, K>())) void lp_pfi_kernel(DevLP 
     }
     if (__any(bad)) {
       if (lane == 0) {
+        const LpIO &io = karg<LpIO>(offsetof(PfiArgs, io));
+        const PfiIO &px = karg<PfiIO>(offsetof(PfiArgs, px));
         write_unsolved(io, b, 2);
         if (io.path.k_out != nullptr) io.path.k_out[b] = 0;
         if (px.decide) {   // ProvenInfeasible (node_decide: 1)
@@ -769,7 +822,7 @@ __global__ __launch_bounds__((64 * waves_for<S, K>())) void lp_pfi_kernel(DevLP 
       }
 
       // ---- FTRAN: alpha_q = E...E B0^{-1} a_q ----
-      const double alq = apply_etas(ftran_col0(P, px.t0, q, lane), eta, prow, ne, lane);
+      const double alq = apply_etas(ftran_col0(P, px.t0, q, lane), eta, prow, ne, lane, 1);
       const double arq = rld(alq, r);
       PSTAMP(6);
 
@@ -787,9 +840,10 @@ __global__ __launch_bounds__((64 * waves_for<S, K>())) void lp_pfi_kernel(DevLP 
       // ---- eta column of this pivot (oracle: -alpha_q/alpha_rq, 1/alpha_rq at r)
       const double inv = 1.0 / arq;
       const double e = lane == r ? inv : -alq * inv;
+      const int nes = rfl(ne);   // scalar compares below (see btran_etas)
 #pragma unroll
       for (int t = 0; t < K; ++t)
-        if (t == ne) eta[t] = e;
+        if (t == nes) eta[t] = e;
       if (lane == ne) prow = r;
       ++ne;
       ++iters;
@@ -797,7 +851,9 @@ __global__ __launch_bounds__((64 * waves_for<S, K>())) void lp_pfi_kernel(DevLP 
     }
 
     wave_piv += (unsigned long long)iters;   // this kernel's own pivots
-    // ---- outputs ----
+    // ---- outputs ---- (their arguments: loaded here, see karg)
+    const LpIO &io = karg<LpIO>(offsetof(PfiArgs, io));
+    const PfiIO &px = karg<PfiIO>(offsetof(PfiArgs, px));
     if (status == -1) {
       // overflow: take a list slot; within the slot capacity, hand K3 this
       // basis with its explicit inverse (oracle: the same loops) so it
@@ -817,7 +873,7 @@ __global__ __launch_bounds__((64 * waves_for<S, K>())) void lp_pfi_kernel(DevLP 
         const int li = lane < m ? lane : 0;
         for (int c = 0; c < m; ++c) {
           double v = lane < m ? P.b0[(size_t)c * ld + li] : 0.0;
-          v = apply_etas(v, eta, prow, ne, lane);
+          v = apply_etas(v, eta, prow, ne, lane, 2);
           if (lane < m) cb[(size_t)c * m + lane] = v;  // column-major (ABI layout)
         }
       }
@@ -967,8 +1023,8 @@ hipError_t launch_s(const DevLP &lp, const LpIO &io, const PfiIO &px, int num_cu
   const size_t lds = lp_pfi_lds_bytes(lp.n, lp.m, lp.nnz, px.kmax);
   const int want = (io.batch + kWaves - 1) / kWaves;
   const int blocks = want < num_cus ? want : num_cus;
-  hipLaunchKernelGGL((lp_pfi_kernel<S, K>), dim3(blocks), dim3(64 * kWaves), lds, stream, lp,
-                     io, px);
+  hipLaunchKernelGGL((lp_pfi_kernel<S, K>), dim3(blocks), dim3(64 * kWaves), lds, stream,
+                     PfiArgs{lp, io, px});
   return hipGetLastError();
 }
 
@@ -987,11 +1043,11 @@ hipError_t launch_k(const DevLP &lp, const LpIO &io, const PfiIO &px, int num_cu
 
 #ifdef MGPU_STAMPS
 extern "C" int mgpu_debug_pfi_stamps(unsigned long long *out, int reset) {
-  if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_pfi_stamps), sizeof(unsigned long long) * 16) !=
+  if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_pfi_stamps), sizeof(unsigned long long) * 24) !=
       hipSuccess)
     return -1;
   if (reset) {
-    unsigned long long z[16] = {0};
+    unsigned long long z[24] = {0};
     if (hipMemcpyToSymbol(HIP_SYMBOL(g_pfi_stamps), z, sizeof z) != hipSuccess) return -1;
   }
   return 0;

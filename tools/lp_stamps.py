@@ -44,7 +44,7 @@ def tree():
     ctx.bnb_config(0, int(os.environ.get('PROBE_WARM', '2')))
     ctx.bnb_init(B * 8 + 2)
     ctx.bnb_import(LB, UB, np.full(B, -math.inf), np.zeros(B, dtype=np.int32))
-    buf = (ctypes.c_ulonglong * 16)()
+    buf = (ctypes.c_ulonglong * 24)()
     st = None
     for r in range(5):
         if r == 4:
@@ -58,6 +58,13 @@ def tree():
     print(f"round 4: pivots {piv}  total wave-cycles {tot:.3e}  per pivot {tot / max(piv, 1):.0f}")
     for i, nme in enumerate(names):
         print(f"  {nme:14s} {100.0 * buf[i] / tot:6.2f} %   {buf[i] / max(piv, 1):9.0f} cyc/pivot")
+    # forward eta steps per call site and the share whose pivot component is
+    # zero (the step changes nothing: apply_etas's select keeps v)
+    for i, nme in enumerate(('primals', 'ftran', 'continuation', 'path replay')):
+        nz, z = buf[16 + 2 * i], buf[17 + 2 * i]
+        if nz + z:
+            print(f"  eta steps {nme:13s} {(nz + z) / max(piv, 1):7.2f} per pivot, "
+                  f"v_p == 0 in {100.0 * z / (nz + z):5.1f} %")
 
 
 def b1():
@@ -157,7 +164,7 @@ def main():
     B = 65536
     LB, UB = random_boxes(p, B, 20261015)
     f = ctx.fbbt(LB, UB)
-    buf = (ctypes.c_ulonglong * 16)()
+    buf = (ctypes.c_ulonglong * 24)()   # mgpu_debug_pfi_stamps writes 24
     if pfi:
         ctx.set_lp_variant(3)
         fn, names = lib.mgpu_debug_pfi_stamps, PFI_NAMES
