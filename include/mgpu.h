@@ -110,6 +110,27 @@ int mgpu_fbbt_dev(mgpu_ctx *ctx, int batch, const double *d_lb_in,
                   double *d_ub_out, int32_t *d_infeasible, int32_t *d_nmods,
                   int mod_cap, int32_t *d_mod_var, int32_t *d_mod_lu,
                   double *d_mod_val);
+/* mgpu_fbbt_dev with clean-row masks (m <= 64; device arrays, each may be
+ * null).  d_init_mask[b] (u64, null = all rows): bit r clear promises that
+ * visiting row r of node b now would change no bound and prove nothing, so
+ * the node's first sweep skips it.  d_carry_out[b]: that mask for the
+ * node's output box -- the row flags left when its sweep loop ended plus
+ * every row whose last visit proved the node infeasible (simplePresolve
+ * ignores that verdict, and a revisit ends the sweep at that row again).
+ * The mask of a child that moves one bound of column j of the output box is
+ * carry | (rows holding j).  d_order (i32, a permutation of [0, batch), null
+ * = identity): the kernel works through nodes d_order[0], d_order[1], ...;
+ * every array keeps the node's own index.  Outputs are bit-identical to
+ * mgpu_fbbt_dev's whatever the masks, as long as they keep the promise.
+ * Kernels that do not take masks (m > 64, the LDS variant, K1G, a mod log)
+ * ignore them and return all-ones in d_carry_out. */
+int mgpu_fbbt_masked_dev(mgpu_ctx *ctx, int batch, const double *d_lb_in,
+                         const double *d_ub_in, double incumbent,
+                         double *d_lb_out, double *d_ub_out,
+                         int32_t *d_infeasible, int32_t *d_nmods, int mod_cap,
+                         int32_t *d_mod_var, int32_t *d_mod_lu,
+                         double *d_mod_val, const uint64_t *d_init_mask,
+                         uint64_t *d_carry_out, const int32_t *d_order);
 
 /* Batched LP relaxation solves: for every node box b, what
  * OsiLPEngine::solve (OsiLPEngine.cpp:571-652) returns for the loaded rows
@@ -437,6 +458,14 @@ int mgpu_bnb_relaxation(mgpu_ctx *ctx, int kind);
  * the variable toward the incumbent's value comes first.  Order 2 only (the
  * other orders place children by slot). */
 int mgpu_bnb_guided_dive(mgpu_ctx *ctx, int on);
+
+/* Clean-row masks in the next mgpu_bnb_init's tree (depth-first order, m <=
+ * 64): 0 off (every node's FBBT starts from all rows), 1 every child starts
+ * from its parent's carried mask plus the rows of its branching variable
+ * (mgpu_fbbt_masked_dev), 2 (default) also works through a round's nodes
+ * grouped by branching variable, so that the nodes of a wave share their
+ * rows.  The tree is the same in every mode. */
+int mgpu_bnb_fbbt_carry(mgpu_ctx *ctx, int mode);
 
 /* Brancher of the next mgpu_bnb_init: 0 MaxVioBrancher (default), 1
  * ReliabilityBrancher (the reference's default, ReliabilityBrancher.cpp) with

@@ -90,6 +90,13 @@ struct BnbState {
   // rebalance inside a timed multi-GPU run allocates nothing once warm
   DevBuf mw_slots, mw_ft, mw_tmp, mw_tlb, mw_tub, mw_tnlb, mw_tdep;
   std::vector<int> pick;       // mgpu_bnb_pick: pool slots of the picked nodes, in pick order
+  // clean-row masks (mgpu_bnb_fbbt_carry; depth-first, m <= 64): per pool
+  // slot the node's K1 start mask and its parent's branching variable (-1:
+  // none, all rows), per batch the masks K1 carries out, and the grouping
+  // pass's sort buffers (keys, node indices, the order K1 works through)
+  int carry = 0;               // the mode at init, 0 when the tree cannot use masks
+  size_t osort_bytes = 0;
+  DevBuf pmask, pkey, bcarry, okeys, okeys2, ovals, ord, osort_tmp;
   std::vector<DevBuf *> bufs() {
     return {&plb, &pub, &pnlb, &pdepth, &wlb, &wub, &inf, &nm, &st, &obj, &it, &x,
                       &dec, &cand, &bvar, &bval, &bup, &depth_in, &pos, &bsum, &bidx, &boff,
@@ -102,7 +109,8 @@ struct BnbState {
                       &rcnt, &clb, &cub, &cnode, &cst, &cobj, &cit, &ev_off, &cv_var, &cv_side,
                       &cv_cost, &ppk, &ppath, &ppst, &bpk, &bppath, &bpst, &opk, &oppath, &opst,
                       &cslots, &ch_head, &ch_st, &ch_d, &ch_binv, &sbstop, &sblist, &sbcnt,
-                      &mw_slots, &mw_ft, &mw_tmp, &mw_tlb, &mw_tub, &mw_tnlb, &mw_tdep};
+                      &mw_slots, &mw_ft, &mw_tmp, &mw_tlb, &mw_tub, &mw_tnlb, &mw_tdep,
+                      &pmask, &pkey, &bcarry, &okeys, &okeys2, &ovals, &ord, &osort_tmp};
   }
   void release() {
     for (DevBuf *b : bufs()) b->release();
@@ -129,6 +137,13 @@ void bnb_state_free(mgpu_ctx *c) {
 
 namespace {
 
+// key bits of the grouping sort: branching variable + 1 in [0, n]
+int order_bits(int n) {
+  int bits = 1;
+  while (bits < 32 && (1u << bits) < (unsigned)n + 1u) ++bits;
+  return bits;
+}
+
 int ensure_batch(mgpu_ctx *c, BnbState &s, int B) {
   if (B <= s.maxb) return MGPU_OK;
   const size_t n = (size_t)s.n, m = (size_t)c->lp.m;
@@ -144,6 +159,18 @@ int ensure_batch(mgpu_ctx *c, BnbState &s, int B) {
   HIPCHK(c, s.bmin.ensure(nblk * 8));
   HIPCHK(c, s.bcnt.ensure(nblk * 8 * 4));
   HIPCHK(c, s.out.ensure(sizeof(BnbOut)));
+  if (s.carry) {
+    HIPCHK(c, s.bcarry.ensure((size_t)B * 8));
+    if (s.carry == 2) {
+      for (DevBuf *b : {&s.okeys, &s.okeys2, &s.ovals, &s.ord}) HIPCHK(c, b->ensure((size_t)B * 4));
+      size_t tb = 0;
+      HIPCHK(c, bnb_sort_keys32(nullptr, tb, s.okeys.as<uint32_t>(), s.okeys2.as<uint32_t>(),
+                                s.ovals.as<uint32_t>(), s.ord.as<uint32_t>(), B, order_bits(s.n),
+                                c->stream));
+      HIPCHK(c, s.osort_tmp.ensure(tb + 16));
+      s.osort_bytes = tb;
+    }
+  }
   if (s.rel) {
     for (DevBuf *b : {&s.bpvar, &s.rflag, &s.rrank, &s.nsb, &s.sb_off, &s.dec2, &s.nev,
                       &s.ev_off})
@@ -431,6 +458,14 @@ int mgpu_bnb_relaxation(mgpu_ctx *c, int kind) {
   return MGPU_OK;
 }
 
+int mgpu_bnb_fbbt_carry(mgpu_ctx *c, int mode) {
+  if (!c) return MGPU_ERR_ARG;
+  if (mode < 0 || mode > 2)
+    return fail(c, MGPU_ERR_ARG, "mgpu_bnb_fbbt_carry: 0 (off), 1 (masks) or 2 (masks + grouping)");
+  c->bnb_carry = mode;
+  return MGPU_OK;
+}
+
 int mgpu_bnb_growth(mgpu_ctx *c, int div) {
   if (!c) return MGPU_ERR_ARG;
   if (div < 0) return fail(c, MGPU_ERR_ARG, "mgpu_bnb_growth: div must be >= 0");
@@ -469,6 +504,14 @@ int mgpu_bnb_init(mgpu_ctx *c, int capacity, const double *root_lb, const double
   s->rel = c->bnb_brancher;
   s->qp = c->bnb_relax;
   s->grow = c->bnb_grow;
+  // children start K1 from their parent's clean rows: the depth-first stack
+  // (its popped slice is read in place) with the row flags as one bit mask
+  s->carry = (s->order == 0 && m <= 64) ? c->bnb_carry : 0;
+  // MGPU_BNB_CARRY (A/B runs of the benchmark) overrides the mode
+  if (const char *e = std::getenv("MGPU_BNB_CARRY")) {
+    const int v = std::atoi(e);
+    if (s->carry && v >= 0 && v <= 2) s->carry = v;
+  }
   s->tot.incumbent = incumbent;
   if (s->qp && (!c->qp || s->warm != 0 || s->rel))
     return fail(c, MGPU_ERR_ARG, "mgpu_bnb_init: QP relaxations need mgpu_load_qp (same columns as "
@@ -511,6 +554,12 @@ int mgpu_bnb_init(mgpu_ctx *c, int capacity, const double *root_lb, const double
   HIPCHK(c, s->pub.ensure((size_t)capacity * n * 8));
   HIPCHK(c, s->pnlb.ensure((size_t)capacity * 8));
   HIPCHK(c, s->pdepth.ensure((size_t)capacity * 4));
+  if (s->carry) {   // the root: all rows, no branching variable (-1)
+    HIPCHK(c, s->pmask.ensure((size_t)capacity * 8));
+    HIPCHK(c, s->pkey.ensure((size_t)capacity * 4));
+    HIPCHK(c, hipMemsetAsync(s->pmask.p, 0xFF, 8, c->stream));
+    HIPCHK(c, hipMemsetAsync(s->pkey.p, 0xFF, 4, c->stream));
+  }
   HIPCHK(c, s->ws_head.ensure((size_t)m * 4 + 4));
   HIPCHK(c, s->ws_st.ensure((size_t)N + 4));
   HIPCHK(c, s->ws_d.ensure((size_t)N * 8));
@@ -747,9 +796,26 @@ int mgpu_bnb_round(mgpu_ctx *c, int batch, double incumbent, mgpu_bnb_stats *sta
   }
   // LinearHandler::varBndsFromObj_ propagates a linear objective only: a
   // QP's node FBBT runs without the incumbent
-  rc = mgpu_fbbt_dev(c, nb, lb, ub, s.qp ? INFINITY : s.inc, s.wlb.as<double>(),
-                     s.wub.as<double>(), s.inf.as<int32_t>(), s.nm.as<int32_t>(), 0, nullptr,
-                     nullptr, nullptr);
+  // clean-row masks (s.carry; depth-first): the popped slice's start masks in
+  // place, the carried masks into the batch buffer for the children writer;
+  // mode 2 with a K1 kernel that takes them: the nodes in the order of their
+  // parents' branching variables (a stable one-pass radix sort), so that a
+  // wave's nodes share their few flagged rows
+  const uint64_t *k1_mask = s.carry ? s.pmask.as<uint64_t>() + base : nullptr;
+  uint64_t *k1_carry = s.carry ? s.bcarry.as<uint64_t>() : nullptr;
+  const int32_t *k1_order = nullptr;
+  if (s.carry == 2 && nb > kLanes && fbbt_masks_apply(c, nb)) {
+    HIPCHK(c, launch_bnb_order_keys(s.pkey.as<int32_t>() + base, nb, s.okeys.as<uint32_t>(),
+                                    s.ovals.as<uint32_t>(), c->stream));
+    size_t tb = s.osort_bytes;
+    HIPCHK(c, bnb_sort_keys32(s.osort_tmp.p, tb, s.okeys.as<uint32_t>(), s.okeys2.as<uint32_t>(),
+                              s.ovals.as<uint32_t>(), s.ord.as<uint32_t>(), nb, order_bits(n),
+                              c->stream));
+    k1_order = s.ord.as<int32_t>();
+  }
+  rc = mgpu_fbbt_masked_dev(c, nb, lb, ub, s.qp ? INFINITY : s.inc, s.wlb.as<double>(),
+                            s.wub.as<double>(), s.inf.as<int32_t>(), s.nm.as<int32_t>(), 0,
+                            nullptr, nullptr, nullptr, k1_mask, k1_carry, k1_order);
   if (rc != MGPU_OK) return rc;
   // the node decision (shouldPrune_ + isFeasible + MaxVio), fused into K3P's
   // epilogue when the round's LPs run the product form (no x read back)
@@ -837,6 +903,12 @@ int mgpu_bnb_round(mgpu_ctx *c, int batch, double incumbent, mgpu_bnb_stats *sta
   if (s.rel) {
     io.ppvar = s.ppvar.as<int32_t>();
     io.ppval = s.ppval.as<double>();
+  }
+  if (s.carry) {
+    io.carry = s.bcarry.as<uint64_t>();
+    io.colmask = c->colmask.as<uint64_t>();
+    io.pmask = s.pmask.as<uint64_t>();
+    io.pkey = s.pkey.as<int32_t>();
   }
   io.status = s.st.as<int32_t>();
   io.iters = s.it.as<int32_t>();
@@ -996,6 +1068,10 @@ int mgpu_bnb_shard(mgpu_ctx *c, int rank, int world, int *kept) {
       rows.push_back({&s.ppvar, 4});
       rows.push_back({&s.ppval, 8});
     }
+    if (s.carry) {
+      rows.push_back({&s.pmask, 8});
+      rows.push_back({&s.pkey, 4});
+    }
     size_t most = 0;
     for (auto &r : rows) most = r.second > most ? r.second : most;
     DevBuf &tmp = s.mw_tmp;
@@ -1126,6 +1202,10 @@ std::vector<std::pair<DevBuf *, size_t>> slot_rows(BnbState &s, int m) {
     r.push_back({&s.ppvar, 4});
     r.push_back({&s.ppval, 8});
   }
+  if (s.carry) {
+    r.push_back({&s.pmask, 8});
+    r.push_back({&s.pkey, 4});
+  }
   return r;
 }
 
@@ -1255,6 +1335,10 @@ int place_nodes(mgpu_ctx *c, BnbState &s, int k, const double *buf) {
   io.pdepth = s.pdepth.as<int32_t>();
   io.plive = s.order == 1 ? s.plive.as<uint8_t>() : nullptr;
   io.ppvar = s.rel ? s.ppvar.as<int32_t>() : nullptr;
+  if (s.carry) {   // a placed node starts K1 from all rows
+    io.pmask = s.pmask.as<uint64_t>();
+    io.pkey = s.pkey.as<int32_t>();
+  }
   if (s.warm == 2) {  // the basis each row carries (k 0: the root basis)
     io.ppk = s.ppk.as<int32_t>();
     io.ppath = s.ppath.as<uint32_t>();

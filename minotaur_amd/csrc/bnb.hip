@@ -206,6 +206,10 @@ __global__ __launch_bounds__(256) void bnb_children(BnbIO io, int n) {
       io.pdepth[c] = io.depth_in[i];
       if (io.plive != nullptr) io.plive[c] = 1;
       if (io.ppvar != nullptr) io.ppvar[c] = -1;
+      if (io.pmask != nullptr) {  // solved again from all rows
+        io.pmask[c] = ~0ull;
+        io.pkey[c] = -1;
+      }
     }
     return;
   }
@@ -287,6 +291,15 @@ __global__ __launch_bounds__(256) void bnb_children(BnbIO io, int n) {
       io.ppvar[c_up] = j;
       io.ppval[c_down] = v;
       io.ppval[c_up] = v;
+    }
+    if (io.pmask != nullptr) {
+      // the child's box is the node's K1 output with one bound of column j
+      // moved: the rows K1 left unclean plus the rows holding j
+      const uint64_t mk = io.carry[i] | io.colmask[j];
+      io.pmask[c_down] = mk;
+      io.pmask[c_up] = mk;
+      io.pkey[c_down] = j;
+      io.pkey[c_up] = j;
     }
   }
 }

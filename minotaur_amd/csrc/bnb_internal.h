@@ -55,6 +55,14 @@ struct BnbIO {
   const int32_t *decision;      // [nb] (5: one child with the bound change bvar/bval/bup)
   int32_t *ppvar;               // [cap] or null: the children's parent branching variable
   double *ppval;                //   and its value (reliability branching's pseudocosts)
+  // clean-row masks (pmask != null): a child starts K1 from the rows its
+  // parent's K1 left unclean (carry, batch-indexed) plus the rows holding
+  // its branching variable (colmask), which is also its grouping key; a
+  // node modified by the brancher starts from all rows, key -1
+  const uint64_t *carry;        // [nb]
+  const uint64_t *colmask;      // [n]
+  uint64_t *pmask;              // [cap]
+  int32_t *pkey;                // [cap]
   const int32_t *status;        // [nb] LP status (12 = not solved: FBBT-infeasible)
   const int32_t *iters;         // [nb] LP pivots
   int pfi_cap;                  // product-form eta cap of the round's LP call (0: dense)
@@ -178,6 +186,14 @@ hipError_t bnb_sort_pairs(void *tmp, size_t &tmp_bytes, const uint64_t *keys_in,
                           uint64_t *keys_out, const uint32_t *vals_in, uint32_t *vals_out,
                           int count, hipStream_t stream);
 hipError_t launch_bnb_gather(const BnbSelIO &io, hipStream_t stream);
+// K1's node order of a round (clean-row masks, grouping): keys[i] = key[i] +
+// 1 and vals[i] = i, then a stable radix sort of the pairs on the keys' low
+// `bits` bits; vals_out is the order
+hipError_t launch_bnb_order_keys(const int32_t *key, int nb, uint32_t *keys, uint32_t *vals,
+                                 hipStream_t stream);
+hipError_t bnb_sort_keys32(void *tmp, size_t &tmp_bytes, const uint32_t *keys_in,
+                           uint32_t *keys_out, const uint32_t *vals_in, uint32_t *vals_out,
+                           int count, int bits, hipStream_t stream);
 hipError_t launch_sb_boxes(const double *plb, const double *pub, const int32_t *var,
                            const double *val, int ncand, int n, double *clb, double *cub,
                            hipStream_t stream);
@@ -208,6 +224,8 @@ struct MigrateIO {
   int32_t *pdepth;
   uint8_t *plive;               // best-first pool flags (null: stack)
   int32_t *ppvar;               // reliability: parent branching variable (null: none)
+  uint64_t *pmask;              // clean-row masks (null: none) <- all rows,
+  int32_t *pkey;                //   no branching variable (-1)
   int32_t *ppk;                 // warm mode 2: the rows' bases (null: none)
   uint32_t *ppath;
   int8_t *ppst;

@@ -85,6 +85,10 @@ __global__ __launch_bounds__(256) void bnb_unpack(MigrateIO io) {
     io.pdepth[s] = (int32_t)row[2 * n + 1];
     if (io.plive) io.plive[s] = 1;
     if (io.ppvar) io.ppvar[s] = -1;   // no parent branching data
+    if (io.pmask) {                   // K1 from all rows
+      io.pmask[s] = ~0ull;
+      io.pkey[s] = -1;
+    }
   }
   if (io.ppk) {   // warm mode 2: the basis the row carries (k 0: the root's)
     const int N = io.N;

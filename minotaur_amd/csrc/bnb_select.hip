@@ -108,6 +108,33 @@ hipError_t bnb_sort_pairs(void *tmp, size_t &tmp_bytes, const uint64_t *keys_in,
                                    (unsigned int)count, 0, 64, stream);
 }
 
+namespace {
+
+__global__ __launch_bounds__(256) void bnb_order_keys(const int32_t *key, int nb, uint32_t *keys,
+                                                      uint32_t *vals) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= nb) return;
+  keys[i] = (uint32_t)(key[i] + 1);   // -1 (no branching variable) first
+  vals[i] = (uint32_t)i;
+}
+
+}  // namespace
+
+hipError_t launch_bnb_order_keys(const int32_t *key, int nb, uint32_t *keys, uint32_t *vals,
+                                 hipStream_t stream) {
+  if (nb <= 0) return hipSuccess;
+  hipLaunchKernelGGL(bnb_order_keys, dim3((nb + 255) / 256), dim3(256), 0, stream, key, nb, keys,
+                     vals);
+  return hipGetLastError();
+}
+
+hipError_t bnb_sort_keys32(void *tmp, size_t &tmp_bytes, const uint32_t *keys_in,
+                           uint32_t *keys_out, const uint32_t *vals_in, uint32_t *vals_out,
+                           int count, int bits, hipStream_t stream) {
+  return rocprim::radix_sort_pairs(tmp, tmp_bytes, keys_in, keys_out, vals_in, vals_out,
+                                   (unsigned int)count, 0, (unsigned int)bits, stream);
+}
+
 hipError_t launch_bnb_gather(const BnbSelIO &io, hipStream_t stream) {
   if (io.nb <= 0) return hipSuccess;
   hipLaunchKernelGGL(bnb_gather, dim3((io.nb + 3) / 4), dim3(256), 0, stream, io);

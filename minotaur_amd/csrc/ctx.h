@@ -60,6 +60,7 @@ struct mgpu_ctx {
   // problem storage
   DevBuf rowptr, terms, rlo, rhi, colptr, rowidx, vtype, obj, collb, colub, objd;
   DevBuf rows, trec, orec, irec, ccont, cval, ccol, rval;
+  DevBuf colmask;              // [n] u64: rows holding each column (TermRec::cmask; 0 when m > 64)
   // LP workspaces (host-pointer path)
   DevBuf lp_lb, lp_ub, lp_skip, lp_wh, lp_wst, lp_wd, lp_wb, lp_st, lp_obj, lp_it, lp_x,
       lp_oh, lp_ost, lp_od, lp_ob;
@@ -79,6 +80,7 @@ struct mgpu_ctx {
   int bnb_brancher = 0;        // mgpu_bnb_brancher: 0 MaxVio, 1 reliability
   int bnb_guided = 1;          // mgpu_bnb_guided_dive (order 2: child order by the incumbent)
   int bnb_grow = 0;            // mgpu_bnb_growth: batch <= nodes so far / div (0: off)
+  int bnb_carry = 2;           // mgpu_bnb_fbbt_carry: 0 off, 1 clean-row masks, 2 + grouping
   bool sb_chain = true;        // mgpu_set_sb_chain: strong-branching chains in one K3 launch
   DevBuf lp_slots;             // K3L: one B^-1 [m][m] per resident workgroup
   DevBuf lp_next;              // K3L: node counter of the dynamic schedule
@@ -187,3 +189,6 @@ int lp_solve_rows_wo(mgpu_ctx *c, int batch, const double *lb, const double *ub,
 // mgpu_lp_solve (mgpu_runtime.cpp); io.next is set here
 int launch_lp_nodes(mgpu_ctx *c, const LpIO &io);
 bool lp_chain_ok(const mgpu_ctx *c);
+// mgpu_fbbt_masked_dev would honour masks and order for a batch of this size
+// (mgpu_runtime.cpp)
+bool fbbt_masks_apply(const mgpu_ctx *c, int batch);

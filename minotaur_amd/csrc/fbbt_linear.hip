@@ -163,6 +163,27 @@ __device__ __forceinline__ void box_out(const V &v, double *dst_l, double *dst_u
   }
 }
 
+// The rows of a node whose LAST visit proved it infeasible (FbbtIO::
+// carry_out must keep them: simplePresolve ignores the verdict, and a child
+// that revisits the row stops its sweep there again).  One register: the
+// one such row in bits 0-5 with bit 8, or bit 9 once a second row held a
+// verdict at the same time (rare; the mask is then "all rows", which is
+// always correct).  Two more VGPRs for an exact 64-bit mask spill in the
+// persistent kernel.
+struct InfRows {
+  unsigned st;
+  // after each visit of row r (wave-uniform), inf = its verdict
+  __device__ __forceinline__ void visit(int r, bool inf) {
+    const unsigned tag = 0x100u | (unsigned)r;
+    if ((st & 0x3ffu) == tag) st = 0u;       // the row's earlier verdict is superseded
+    if (inf) st = (st & 0x300u) ? 0x200u : tag;
+  }
+  __device__ __forceinline__ uint64_t mask(uint64_t all_rows) const {
+    if (st & 0x200u) return all_rows;
+    return (st & 0x100u) ? 1ull << (st & 63u) : 0ull;
+  }
+};
+
 struct NodeState {
   int nmods;
   unsigned nintmods;
@@ -653,6 +674,14 @@ __global__ __launch_bounds__(kLanes) void fbbt_linear_kernel(DevLP lp, FbbtIO io
   const int b0 = blockIdx.x * io.npw;
   const int nb = min(io.npw, io.batch - b0);
   const int n = lp.n, m = lp.m;
+  // clean-row masks and the node order (FbbtIO): the bit-flag kernel on the
+  // global scratch only
+  constexpr bool kMasks = kBitFlags && !kLds;
+  const uint64_t all_rows = m >= 64 ? ~0ull : ((1ull << m) - 1ull);
+  int node = b0 + lane;   // this lane's node (lane < nb)
+  if constexpr (kMasks)
+    if (lane < nb && io.order != nullptr) node = io.order[b0 + lane];
+  InfRows inf_rows{0u};
 
   NodeView<kBitFlags, !kLds> v;
   v.lane = lane;
@@ -696,7 +725,7 @@ __global__ __launch_bounds__(kLanes) void fbbt_linear_kernel(DevLP lp, FbbtIO io
   // coalesced 512-B scratch row.  LDS variant: node-outer, coalesced reads.
   if constexpr (!kLds) {
     if (lane < nb)
-      box_in(v, io.lb_in + (size_t)(b0 + lane) * n, io.ub_in + (size_t)(b0 + lane) * n, n);
+      box_in(v, io.lb_in + (size_t)node * n, io.ub_in + (size_t)node * n, n);
   }
   for (int nd = 0; nd < (kLds ? nb : 0); ++nd) {
     const double *src_l = io.lb_in + (size_t)(b0 + nd) * n;
@@ -708,7 +737,9 @@ __global__ __launch_bounds__(kLanes) void fbbt_linear_kernel(DevLP lp, FbbtIO io
   }
   // simplePresolve: every constraint's BFlag set (LinearHandler.cpp:1618-1622)
   if constexpr (kBitFlags) {
-    v.bits = m >= 64 ? ~0ull : ((1ull << m) - 1ull);
+    v.bits = all_rows;
+    if constexpr (kMasks)
+      if (lane < nb && io.init_mask != nullptr) v.bits &= io.init_mask[node];
   } else {
     for (int r = 0; r < m; ++r) v.flag[r * kLanes + lane] = 1;
   }
@@ -718,7 +749,7 @@ __global__ __launch_bounds__(kLanes) void fbbt_linear_kernel(DevLP lp, FbbtIO io
   NodeState s{0, 0u};
   ModLog log{nullptr, nullptr, nullptr, io.mod_cap};
   if (io.mod_var != nullptr && io.mod_cap > 0 && live) {
-    const size_t o = (size_t)(b0 + lane) * io.mod_cap;
+    const size_t o = (size_t)node * io.mod_cap;
     log.var = io.mod_var + o;
     log.lu = io.mod_lu + o;
     log.val = io.mod_val + o;
@@ -767,6 +798,7 @@ __global__ __launch_bounds__(kLanes) void fbbt_linear_kernel(DevLP lp, FbbtIO io
           else if (nt <= 11) inf = rc_lin_bnd_tighten<11>(nt, trec + k0, rlo, rhi, v, s, log, tch);
           else if (nt <= 16) inf = rc_lin_bnd_tighten<16>(nt, trec + k0, rlo, rhi, v, s, log, tch);
           else inf = lin_bnd_tighten(trec + k0, nt, rlo, rhi, v, s, log, tch);
+          if constexpr (kMasks) inf_rows.visit(r, inf);
           if (inf) {
             cons_on = false;
           } else if (tch) {
@@ -784,13 +816,15 @@ __global__ __launch_bounds__(kLanes) void fbbt_linear_kernel(DevLP lp, FbbtIO io
     if (go) infeas = bad;
   }
   if (live) {
-    io.infeas[b0 + lane] = infeas ? 1 : 0;
-    io.nmods[b0 + lane] = s.nmods;
+    io.infeas[node] = infeas ? 1 : 0;
+    io.nmods[node] = s.nmods;
+    if constexpr (kMasks)
+      if (io.carry_out != nullptr) io.carry_out[node] = v.bits | inf_rows.mask(all_rows);
   }
   __syncthreads();
   if constexpr (!kLds) {  // var-outer: coalesced scratch reads (as the staging)
     if (kFbbtOutVarOuter && lane < nb)
-      box_out(v, io.lb_out + (size_t)(b0 + lane) * n, io.ub_out + (size_t)(b0 + lane) * n, n);
+      box_out(v, io.lb_out + (size_t)node * n, io.ub_out + (size_t)node * n, n);
   }
   for (int nd = 0; nd < (kLds || !kFbbtOutVarOuter ? nb : 0); ++nd) {
     double *dst_l = io.lb_out + (size_t)(b0 + nd) * n;
@@ -860,11 +894,15 @@ __global__ __launch_bounds__(kLanes * kWG, 3) void fbbt_linear_persist(DevLP lp,
 
   int node = -1;
   bool has = false, changed = false, infeas = false, exhausted = false;
-  unsigned iters = 1;
+  // the node's sweep count (bits 0-3, at most 11) and its InfRows state (bits
+  // 4 up) share a register: the kernel is at its VGPR limit for three waves
+  // per SIMD
+  unsigned it_st = 1u;
   NodeState s{0, 0u};
   ModLog log{nullptr, nullptr, nullptr, io.mod_cap};
   while (true) {
-    bool go = has && changed && iters <= 10u && (iters <= 2u || s.nintmods > 0u) && !infeas;
+    bool go = has && changed && (it_st & 15u) <= 10u &&
+              ((it_st & 15u) <= 2u || s.nintmods > 0u) && !infeas;
     // retire: nodes whose sweep loop ended (checked at the sweep boundary,
     // exactly where simplePresolve's loop test runs, LinearHandler.cpp:1625)
     const bool fin = has && !go;
@@ -872,6 +910,8 @@ __global__ __launch_bounds__(kLanes * kWG, 3) void fbbt_linear_persist(DevLP lp,
       if (fin) {
         io.infeas[node] = infeas ? 1 : 0;
         io.nmods[node] = s.nmods;
+        if (io.carry_out != nullptr)
+          io.carry_out[node] = v.bits | InfRows{it_st >> 4}.mask(all_rows);
         box_out(v, io.lb_out + (size_t)node * n, io.ub_out + (size_t)node * n, n);
         has = false;
       }
@@ -888,16 +928,17 @@ __global__ __launch_bounds__(kLanes * kWG, 3) void fbbt_linear_persist(DevLP lp,
         if (!has) {
           const int my = base + __popcll(idle & lt_mask);
           if (my < io.batch) {
-            node = my;
+            node = io.order != nullptr ? io.order[my] : my;
             has = true;
             box_in(v, io.lb_in + (size_t)node * n, io.ub_in + (size_t)node * n, n);
-            // simplePresolve: every constraint's BFlag set (:1618-1622)
-            v.bits = all_rows;
+            // simplePresolve: every constraint's BFlag set (:1618-1622), less
+            // the rows the caller knows to be clean
+            v.bits = io.init_mask != nullptr ? io.init_mask[node] & all_rows : all_rows;
             s.nmods = 0;
             s.nintmods = 0u;
             changed = true;
             infeas = false;
-            iters = 1;
+            it_st = 1u;
             log = ModLog{nullptr, nullptr, nullptr, io.mod_cap};
             if (io.mod_var != nullptr && io.mod_cap > 0) {
               const size_t o = (size_t)node * io.mod_cap;
@@ -917,7 +958,7 @@ __global__ __launch_bounds__(kLanes * kWG, 3) void fbbt_linear_persist(DevLP lp,
     if (go) {
       s.nintmods = 0u;
       changed = false;
-      ++iters;
+      ++it_st;
     }
     bool cons_on = go;
     for (int r0 = 0; r0 < m; r0 += kLanes) {
@@ -943,6 +984,9 @@ __global__ __launch_bounds__(kLanes * kWG, 3) void fbbt_linear_persist(DevLP lp,
           else if (nt <= 11) inf = rc_lin_bnd_tighten<11>(nt, trec + k0, rlo, rhi, v, s, log, tch);
           else if (nt <= 16) inf = rc_lin_bnd_tighten<16>(nt, trec + k0, rlo, rhi, v, s, log, tch);
           else inf = lin_bnd_tighten(trec + k0, nt, rlo, rhi, v, s, log, tch);
+          InfRows ir{it_st >> 4};
+          ir.visit(r, inf);
+          it_st = (it_st & 15u) | (ir.st << 4);
           if (inf) {
             cons_on = false;
           } else if (tch) {

@@ -329,6 +329,18 @@ struct FbbtIO {
   uint8_t *flag_scratch;        // global-bounds variant: [waves][m][kLanes]
   int32_t *next;                // persistent variant: zeroed node counter (queue head)
   int refill_min;               // persistent variant: idle lanes before a refill (1 = any)
+  // Clean-row masks (bit-flag kernels with the bounds in the global scratch,
+  // m <= 64; every other kernel ignores them).  A clear bit of init_mask[b]
+  // promises that visiting that row of node b now would change no bound and
+  // return no infeasibility verdict; carry_out[b] is that mask for node b's
+  // output box: the flags left when its sweep loop ended plus every row whose
+  // last visit returned the verdict (the reference ignores the verdict, so a
+  // revisit stops the sweep at that row again).  order: queue position q
+  // works on node order[q] (a permutation of [0, batch)), all of whose
+  // arrays keep the node's own index.
+  const uint64_t *init_mask;    // [B] or null: all rows
+  uint64_t *carry_out;          // [B] or null: not written
+  const int32_t *order;         // [B] or null: identity
 };
 
 constexpr int kLanes = 64;      // wave64: one node per lane

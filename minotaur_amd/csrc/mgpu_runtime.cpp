@@ -64,7 +64,8 @@ int mgpu_destroy(mgpu_ctx *c) {
                     &c->lp_ost, &c->lp_od, &c->lp_ob, &c->lp_slots, &c->io_lb_in,
                     &c->io_ub_in, &c->io_lb_out, &c->io_ub_out, &c->io_inf, &c->io_nmods,
                     &c->io_mv, &c->io_ml, &c->io_mval, &c->scratch, &c->flag_scratch,
-                    &c->fbbt_next, &c->lp_next3, &c->nr_map, &c->nr_ws, &c->nr_vals, &c->pfi_piv})
+                    &c->fbbt_next, &c->lp_next3, &c->nr_map, &c->nr_ws, &c->nr_vals, &c->pfi_piv,
+                    &c->colmask})
     b->release();
   for (auto &ch : c->ws_chunks)
     if (ch.base) (void)hipFree(ch.base);
@@ -231,6 +232,7 @@ int mgpu_load_lp(mgpu_ctx *c, int n, int m, const int32_t *rowptr, const int32_t
   HIPCHK(c, upload(c->orec, orec.data(), orec.size()));
   HIPCHK(c, upload(c->irec, irec.data(), irec.size()));
   HIPCHK(c, upload(c->ccont, ccont.data(), ccont.size()));
+  HIPCHK(c, upload(c->colmask, cmask.data(), cmask.size()));
   HIPCHK(c, upload(c->cval, cvalv.data(), cvalv.size()));
   HIPCHK(c, upload(c->ccol, nnz > 0 ? colidx : rowptr, (size_t)(nnz > 0 ? nnz : 1)));
   HIPCHK(c, upload(c->rval, nnz > 0 ? val : cvalv.data(), (size_t)(nnz > 0 ? nnz : 1)));
@@ -363,6 +365,75 @@ int mgpu_fbbt_dev(mgpu_ctx *c, int batch, const double *lb_in, const double *ub_
                   double incumbent, double *lb_out, double *ub_out, int32_t *infeas,
                   int32_t *nmods, int mod_cap, int32_t *mod_var, int32_t *mod_lu,
                   double *mod_val) {
+  return mgpu_fbbt_masked_dev(c, batch, lb_in, ub_in, incumbent, lb_out, ub_out, infeas, nmods,
+                              mod_cap, mod_var, mod_lu, mod_val, nullptr, nullptr, nullptr);
+}
+
+// The K1 kernel mgpu_fbbt_masked_dev runs a batch with: 1 LDS, 2 one node per
+// lane on the global scratch, 3 persistent, 4..6 K1G; npw: nodes per wave.
+static int fbbt_select(const mgpu_ctx *c, int batch, int mod_cap, int *npw_out) {
+  // nodes per wave: one per lane fills the chip from kFbbtSmallWaves * CUs *
+  // 64 nodes on; a smaller batch (the narrow rounds of a complete tree)
+  // spreads its nodes over that many waves instead: a wave walks the union of
+  // its nodes' flagged rows, so fewer nodes per wave shorten the round's
+  // critical path (a forced variant keeps one node per lane);
+  // MGPU_FBBT_NPW overrides for experiments
+  int npw = kLanes;
+  if (c->fbbt_variant == 0) {
+    const long target = (long)c->num_cus * kFbbtSmallWaves;
+    if ((long)batch < target * kLanes) {
+      const int want = (int)(((long)batch + target - 1) / target);
+      npw = 1;
+      while (npw < want) npw <<= 1;
+    }
+  }
+  if (const char *e = getenv("MGPU_FBBT_NPW")) {
+    const int v = atoi(e);
+    if (v >= 1 && v <= kLanes) npw = v;
+  }
+  if (npw_out) *npw_out = npw;
+  const int waves = (batch + npw - 1) / npw;
+  const bool fits = fbbt_lds_bytes(c->lp.n, c->lp.m) <= 160 * 1024;
+  // Auto: the LDS variant holds one wave per CU when the node bounds take
+  // most of the 160 KiB; beyond that, one node per lane with the bounds in a
+  // global scratch while the batch needs at most 8 waves per CU (131 072
+  // nodes on 256 CUs), and past that the persistent
+  // variant, whose lanes take the next node as soon as theirs finishes
+  // (measured on tls4-lin: 262 144 nodes 4.00 -> 3.45 ms, 524 288 nodes
+  // 6.67 -> 5.58 ms; at 131 072 the one-shot kernel is faster, 1.87 vs
+  // 2.17 ms; tools/fbbt_refill_probe.py).
+  int variant = c->fbbt_variant;
+  // K1G (variant 4): four nodes per wave, 16 lanes each, bounds in LDS.
+  // Auto below kFbbtGroupMax nodes: there one node's chain is the kernel's
+  // critical path and K1G shortens it (tls4-oa: 16 384 nodes 0.75 vs 2.25
+  // ms, 65 536 2.7 vs 3.2 ms); wider batches fill the chip and K1's lanes
+  // per node win (524 288: 7.1 vs 18.7 ms; tools/fbbt_batch_sweep.py,
+  // profiles/r04i)
+  if (variant >= 4) return variant;
+  if (variant == 0 && batch <= kFbbtGroupMax && mod_cap == 0 &&
+      fbbt_group_waves(c->lp, kFbbtGroupG) > 0)
+    return 4;
+  if (variant == 0)
+    variant = (fits && waves <= c->num_cus) ? 1 : (waves > 8 * c->num_cus && npw == kLanes) ? 3 : 2;
+  // persistent path: bit flags (m <= 64) and records staged in 64 KiB of LDS
+  if (variant == 3 && (c->lp.m > 64 || fbbt_persist_lds(c->lp) > 64 * 1024))
+    variant = 2;
+  return variant;
+}
+
+// mgpu_fbbt_masked_dev honours init_mask / carry_out / order for this batch
+// (else the masks are ignored, every row starts flagged and carry_out comes
+// back all-ones): the bit-flag kernels on the global scratch, no mod log
+extern "C++" bool fbbt_masks_apply(const mgpu_ctx *c, int batch) {
+  const int v = fbbt_select(c, batch, 0, nullptr);
+  return c->lp.m <= 64 && (v == 2 || v == 3);
+}
+
+int mgpu_fbbt_masked_dev(mgpu_ctx *c, int batch, const double *lb_in, const double *ub_in,
+                         double incumbent, double *lb_out, double *ub_out, int32_t *infeas,
+                         int32_t *nmods, int mod_cap, int32_t *mod_var, int32_t *mod_lu,
+                         double *mod_val, const uint64_t *init_mask, uint64_t *carry_out,
+                         const int32_t *order) {
   if (!c) return MGPU_ERR_ARG;
   if (!c->loaded) return fail(c, MGPU_ERR_STATE, "mgpu_fbbt: no problem loaded");
   if (batch < 0 || (batch > 0 && (!lb_in || !ub_in || !lb_out || !ub_out || !infeas || !nmods)))
@@ -387,46 +458,25 @@ int mgpu_fbbt_dev(mgpu_ctx *c, int batch, const double *lb_in, const double *ub_
   // (best value - objective constant).
   io.has_inc = std::isfinite(incumbent) ? 1 : 0;
   io.inc_ub = io.has_inc ? incumbent - c->lp.objoff : 0.0;
-  // nodes per wave: one per lane fills the chip from kFbbtSmallWaves * CUs *
-  // 64 nodes on; a smaller batch (the narrow rounds of a complete tree)
-  // spreads its nodes over that many waves instead: a wave walks the union of
-  // its nodes' flagged rows, so fewer nodes per wave shorten the round's
-  // critical path (a forced variant keeps one node per lane);
-  // MGPU_FBBT_NPW overrides for experiments
   int npw = kLanes;
-  if (c->fbbt_variant == 0) {
-    const long target = (long)c->num_cus * kFbbtSmallWaves;
-    if ((long)batch < target * kLanes) {
-      const int want = (int)(((long)batch + target - 1) / target);
-      npw = 1;
-      while (npw < want) npw <<= 1;
-    }
-  }
-  if (const char *e = getenv("MGPU_FBBT_NPW")) {
-    const int v = atoi(e);
-    if (v >= 1 && v <= kLanes) npw = v;
-  }
+  int variant = fbbt_select(c, batch, io.mod_cap, &npw);
   io.npw = npw;
   const int waves = (batch + npw - 1) / npw;
   const bool fits = fbbt_lds_bytes(c->lp.n, c->lp.m) <= 160 * 1024;
-  // Auto: the LDS variant holds one wave per CU when the node bounds take
-  // most of the 160 KiB; beyond that, one node per lane with the bounds in a
-  // global scratch while the batch needs at most 8 waves per CU (131 072
-  // nodes on 256 CUs), and past that the persistent
-  // variant, whose lanes take the next node as soon as theirs finishes
-  // (measured on tls4-lin: 262 144 nodes 4.00 -> 3.45 ms, 524 288 nodes
-  // 6.67 -> 5.58 ms; at 131 072 the one-shot kernel is faster, 1.87 vs
-  // 2.17 ms; tools/fbbt_refill_probe.py).
-  int variant = c->fbbt_variant;
-  // K1G (variant 4): four nodes per wave, 16 lanes each, bounds in LDS.
-  // Auto below kFbbtGroupMax nodes: there one node's chain is the kernel's
-  // critical path and K1G shortens it (tls4-oa: 16 384 nodes 0.75 vs 2.25
-  // ms, 65 536 2.7 vs 3.2 ms); wider batches fill the chip and K1's lanes
-  // per node win (524 288: 7.1 vs 18.7 ms; tools/fbbt_batch_sweep.py,
-  // profiles/r04i)
-  const int gg = variant == 4 ? 16 : variant == 5 ? 8 : variant == 6 ? 4 : kFbbtGroupG;
-  if (variant >= 4 || (variant == 0 && batch <= kFbbtGroupMax && io.mod_cap == 0 &&
-                       fbbt_group_waves(c->lp, gg) > 0)) {
+  // the clean-row masks and the node order: the bit-flag kernels on the
+  // global scratch, without a mod log; everywhere else every row starts
+  // flagged and the carried masks come back all-ones ("all rows" is always a
+  // correct mask)
+  const bool masks = c->lp.m <= 64 && (variant == 2 || variant == 3) && io.mod_cap == 0;
+  if (masks) {
+    io.init_mask = init_mask;
+    io.carry_out = carry_out;
+    io.order = order;
+  } else if (carry_out != nullptr) {
+    HIPCHK(c, hipMemsetAsync(carry_out, 0xFF, (size_t)batch * sizeof(uint64_t), c->stream));
+  }
+  if (variant >= 4) {
+    const int gg = variant == 4 ? 16 : variant == 5 ? 8 : 4;
     if (fbbt_group_waves(c->lp, gg) <= 0 || io.mod_cap > 0)
       return fail(c, MGPU_ERR_ARG, "mgpu_fbbt: K1G needs m <= 64, no mod log and LDS room");
     HIPCHK(c, hipEventRecord(c->ev0, c->stream));
@@ -434,11 +484,6 @@ int mgpu_fbbt_dev(mgpu_ctx *c, int batch, const double *lb_in, const double *ub_
     HIPCHK(c, hipEventRecord(c->ev1, c->stream));
     return MGPU_OK;
   }
-  if (variant == 0)
-    variant = (fits && waves <= c->num_cus) ? 1 : (waves > 8 * c->num_cus && npw == kLanes) ? 3 : 2;
-  // persistent path: bit flags (m <= 64) and records staged in 64 KiB of LDS
-  if (variant == 3 && (c->lp.m > 64 || fbbt_persist_lds(c->lp) > 64 * 1024))
-    variant = 2;
   int grid = waves;
   if (variant == 3) {
     // persistent waves: 12 per CU (three per SIMD at the kernel's 168

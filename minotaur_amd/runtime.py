@@ -48,6 +48,7 @@ EXPORTS = [
     'mgpu_alltoall_rows_dev', 'mgpu_lb_deal', 'mgpu_bnb_rebalance', 'mgpu_alloc_stats',
     'mgpu_bnb_growth', 'mgpu_set_sb_chain', 'mgpu_glob_brancher', 'mgpu_glob_lp_log',
     'mgpu_node_serialize', 'mgpu_node_deserialize',
+    'mgpu_fbbt_masked_dev', 'mgpu_bnb_fbbt_carry',
 ]
 
 COMM_ID_BYTES = 128            # MGPU_COMM_ID_BYTES
@@ -124,6 +125,9 @@ def load_library():
     lib.mgpu_load_lp.argtypes = [_P, _I, _I] + [_P] * 9 + [_D]
     lib.mgpu_fbbt.argtypes = [_P, _I, _P, _P, _D, _P, _P, _P, _P, _I, _P, _P, _P]
     lib.mgpu_fbbt_dev.argtypes = [_P, _I, _P, _P, _D, _P, _P, _P, _P, _I, _P, _P, _P]
+    lib.mgpu_fbbt_masked_dev.argtypes = [_P, _I, _P, _P, _D, _P, _P, _P, _P, _I, _P, _P, _P,
+                                         _P, _P, _P]
+    lib.mgpu_bnb_fbbt_carry.argtypes = [_P, _I]
     lib.mgpu_set_fbbt_variant.argtypes = [_P, _I]
     lib.mgpu_set_lp_variant.argtypes = [_P, _I]
     lib.mgpu_set_lp_pfi.argtypes = [_P, _I]
@@ -534,6 +538,17 @@ class Context:
                                          _dp(nmods), cap, _dp(mod_var), _dp(mod_lu),
                                          _dp(mod_val)), 'mgpu_fbbt_dev')
 
+    def fbbt_masked_dev(self, lb, ub, lb_out, ub_out, infeasible, nmods, incumbent=math.inf,
+                        init_mask=None, carry_out=None, order=None):
+        """fbbt_dev with clean-row masks (mgpu_fbbt_masked_dev): init_mask /
+        carry_out int64 [B] (the u64 row masks' bits), order int32 [B] (a
+        permutation); each may be None."""
+        B = int(lb.shape[0])
+        self._chk(self.lib.mgpu_fbbt_masked_dev(
+            self.h, B, _dp(lb), _dp(ub), float(incumbent), _dp(lb_out), _dp(ub_out),
+            _dp(infeasible), _dp(nmods), 0, None, None, None, _dp(init_mask), _dp(carry_out),
+            _dp(order)), 'mgpu_fbbt_masked_dev')
+
     # -- LP ------------------------------------------------------------------
     def lp_solve(self, lb, ub, ws=None, skip=None, iter_limit=0, want_x=False,
                  want_ws=False) -> LpOut:
@@ -758,6 +773,11 @@ class Context:
     def bnb_guided_dive(self, on):
         """Order 2: guided dive child order (IntVarHandler guided_dive)."""
         self._chk(self.lib.mgpu_bnb_guided_dive(self.h, int(on)), 'mgpu_bnb_guided_dive')
+
+    def bnb_fbbt_carry(self, mode):
+        """Next tree's clean-row masks (mgpu_bnb_fbbt_carry): 0 off, 1 masks,
+        2 masks + nodes grouped by branching variable (default)."""
+        self._chk(self.lib.mgpu_bnb_fbbt_carry(self.h, int(mode)), 'mgpu_bnb_fbbt_carry')
 
     def bnb_brancher(self, kind):
         """Next tree's brancher: 0 MaxVio, 1 reliability (mgpu_bnb_brancher)."""
