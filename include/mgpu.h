@@ -131,6 +131,23 @@ int mgpu_fbbt_masked_dev(mgpu_ctx *ctx, int batch, const double *d_lb_in,
                          int32_t *d_mod_var, int32_t *d_mod_lu,
                          double *d_mod_val, const uint64_t *d_init_mask,
                          uint64_t *d_carry_out, const int32_t *d_order);
+/* mgpu_fbbt_masked_dev with clean columns (the same kernels, and n <= 128;
+ * ignored elsewhere).  d_clean_col[b] = j >= 0 promises that node b's box is
+ * the output box of a node that K1 left feasible, with only column j's bounds
+ * moved since: every integer column's bounds are integral or infinite and
+ * every column passes checkBounds_, except perhaps j.  tightenInts_ and
+ * checkBounds_ then take j and the columns whose bounds a row or the
+ * objective changed in that sweep, not all columns: any other column would
+ * change nothing and pass again.  -1, or a null array, promises nothing.
+ * Outputs are bit-identical to mgpu_fbbt_dev's as long as the promise holds. */
+int mgpu_fbbt_cols_dev(mgpu_ctx *ctx, int batch, const double *d_lb_in,
+                       const double *d_ub_in, double incumbent,
+                       double *d_lb_out, double *d_ub_out,
+                       int32_t *d_infeasible, int32_t *d_nmods, int mod_cap,
+                       int32_t *d_mod_var, int32_t *d_mod_lu,
+                       double *d_mod_val, const uint64_t *d_init_mask,
+                       uint64_t *d_carry_out, const int32_t *d_order,
+                       const int32_t *d_clean_col);
 
 /* Batched LP relaxation solves: for every node box b, what
  * OsiLPEngine::solve (OsiLPEngine.cpp:571-652) returns for the loaded rows
@@ -462,9 +479,10 @@ int mgpu_bnb_guided_dive(mgpu_ctx *ctx, int on);
 /* Clean-row masks in the next mgpu_bnb_init's tree (depth-first order, m <=
  * 64): 0 off (every node's FBBT starts from all rows), 1 every child starts
  * from its parent's carried mask plus the rows of its branching variable
- * (mgpu_fbbt_masked_dev), 2 (default) also works through a round's nodes
- * grouped by branching variable, so that the nodes of a wave share their
- * rows.  The tree is the same in every mode. */
+ * (mgpu_fbbt_masked_dev), 2 also works through a round's nodes grouped by
+ * branching variable, so that the nodes of a wave share their rows, 3
+ * (default) also passes every child's branching variable as its clean
+ * column (mgpu_fbbt_cols_dev).  The tree is the same in every mode. */
 int mgpu_bnb_fbbt_carry(mgpu_ctx *ctx, int mode);
 
 /* Brancher of the next mgpu_bnb_init: 0 MaxVioBrancher (default), 1

@@ -161,7 +161,7 @@ int ensure_batch(mgpu_ctx *c, BnbState &s, int B) {
   HIPCHK(c, s.out.ensure(sizeof(BnbOut)));
   if (s.carry) {
     HIPCHK(c, s.bcarry.ensure((size_t)B * 8));
-    if (s.carry == 2) {
+    if (s.carry >= 2) {
       for (DevBuf *b : {&s.okeys, &s.okeys2, &s.ovals, &s.ord}) HIPCHK(c, b->ensure((size_t)B * 4));
       size_t tb = 0;
       HIPCHK(c, bnb_sort_keys32(nullptr, tb, s.okeys.as<uint32_t>(), s.okeys2.as<uint32_t>(),
@@ -460,8 +460,9 @@ int mgpu_bnb_relaxation(mgpu_ctx *c, int kind) {
 
 int mgpu_bnb_fbbt_carry(mgpu_ctx *c, int mode) {
   if (!c) return MGPU_ERR_ARG;
-  if (mode < 0 || mode > 2)
-    return fail(c, MGPU_ERR_ARG, "mgpu_bnb_fbbt_carry: 0 (off), 1 (masks) or 2 (masks + grouping)");
+  if (mode < 0 || mode > 3)
+    return fail(c, MGPU_ERR_ARG, "mgpu_bnb_fbbt_carry: 0 (off), 1 (masks), 2 (masks + grouping) "
+                                 "or 3 (masks + grouping + clean columns)");
   c->bnb_carry = mode;
   return MGPU_OK;
 }
@@ -510,7 +511,7 @@ int mgpu_bnb_init(mgpu_ctx *c, int capacity, const double *root_lb, const double
   // MGPU_BNB_CARRY (A/B runs of the benchmark) overrides the mode
   if (const char *e = std::getenv("MGPU_BNB_CARRY")) {
     const int v = std::atoi(e);
-    if (s->carry && v >= 0 && v <= 2) s->carry = v;
+    if (s->carry && v >= 0 && v <= 3) s->carry = v;
   }
   s->tot.incumbent = incumbent;
   if (s->qp && (!c->qp || s->warm != 0 || s->rel))
@@ -804,7 +805,7 @@ int mgpu_bnb_round(mgpu_ctx *c, int batch, double incumbent, mgpu_bnb_stats *sta
   const uint64_t *k1_mask = s.carry ? s.pmask.as<uint64_t>() + base : nullptr;
   uint64_t *k1_carry = s.carry ? s.bcarry.as<uint64_t>() : nullptr;
   const int32_t *k1_order = nullptr;
-  if (s.carry == 2 && nb > kLanes && fbbt_masks_apply(c, nb)) {
+  if (s.carry >= 2 && nb > kLanes && fbbt_masks_apply(c, nb)) {
     HIPCHK(c, launch_bnb_order_keys(s.pkey.as<int32_t>() + base, nb, s.okeys.as<uint32_t>(),
                                     s.ovals.as<uint32_t>(), c->stream));
     size_t tb = s.osort_bytes;
@@ -813,9 +814,14 @@ int mgpu_bnb_round(mgpu_ctx *c, int batch, double incumbent, mgpu_bnb_stats *sta
                               c->stream));
     k1_order = s.ord.as<int32_t>();
   }
-  rc = mgpu_fbbt_masked_dev(c, nb, lb, ub, s.qp ? INFINITY : s.inc, s.wlb.as<double>(),
-                            s.wub.as<double>(), s.inf.as<int32_t>(), s.nm.as<int32_t>(), 0,
-                            nullptr, nullptr, nullptr, k1_mask, k1_carry, k1_order);
+  // mode 3: a slot's key is also its clean column.  The children writer sets
+  // it to the branching variable exactly where it derives the child's mask
+  // from the parent's K1 output, and every other slot writer sets -1 with
+  // "all rows"; it moves with the mask in shards and exports.
+  const int32_t *k1_cols = s.carry == 3 ? s.pkey.as<int32_t>() + base : nullptr;
+  rc = mgpu_fbbt_cols_dev(c, nb, lb, ub, s.qp ? INFINITY : s.inc, s.wlb.as<double>(),
+                          s.wub.as<double>(), s.inf.as<int32_t>(), s.nm.as<int32_t>(), 0,
+                          nullptr, nullptr, nullptr, k1_mask, k1_carry, k1_order, k1_cols);
   if (rc != MGPU_OK) return rc;
   // the node decision (shouldPrune_ + isFeasible + MaxVio), fused into K3P's
   // epilogue when the round's LPs run the product form (no x read back)

@@ -80,7 +80,7 @@ struct mgpu_ctx {
   int bnb_brancher = 0;        // mgpu_bnb_brancher: 0 MaxVio, 1 reliability
   int bnb_guided = 1;          // mgpu_bnb_guided_dive (order 2: child order by the incumbent)
   int bnb_grow = 0;            // mgpu_bnb_growth: batch <= nodes so far / div (0: off)
-  int bnb_carry = 2;           // mgpu_bnb_fbbt_carry: 0 off, 1 clean-row masks, 2 + grouping
+  int bnb_carry = 3;           // mgpu_bnb_fbbt_carry: 0 off, 1 clean-row masks, 2 + grouping, 3 + clean columns
   bool sb_chain = true;        // mgpu_set_sb_chain: strong-branching chains in one K3 launch
   DevBuf lp_slots;             // K3L: one B^-1 [m][m] per resident workgroup
   DevBuf lp_next;              // K3L: node counter of the dynamic schedule

@@ -31,6 +31,32 @@
 #include <type_traits>
 
 namespace mgpu {
+
+#ifdef MGPU_K1_STAMPS
+// Diagnostic build only (-DMGPU_K1_STAMPS, tools/k1_stamps.py): s_memtime
+// cycles of the persistent kernel per section, summed over all waves: 0 row
+// loop, 1 objective, 2 tightenInts_ + checkBounds_, 3 refill and staging
+// (box_in), 4 retire and write-out (box_out), 5 the rest (loop control, record
+// staging); never compiled into the product.
+__device__ unsigned long long g_k1_stamps[8];
+#define KSTAMP_DECL unsigned long long st_acc[6] = {0}, st_t = __builtin_amdgcn_s_memtime();
+#define KSTAMP(i)                                               \
+  do {                                                          \
+    const unsigned long long t_ = __builtin_amdgcn_s_memtime(); \
+    st_acc[i] += t_ - st_t;                                     \
+    st_t = t_;                                                  \
+  } while (0)
+#define KSTAMP_FLUSH            \
+  if ((threadIdx.x & 63) == 0)  \
+    for (int i_ = 0; i_ < 6; ++i_) atomicAdd(&g_k1_stamps[i_], st_acc[i_]);
+#else
+#define KSTAMP_DECL
+#define KSTAMP(i) \
+  do {            \
+  } while (0)
+#define KSTAMP_FLUSH
+#endif
+
 namespace {
 
 // write-out order of the global variant: var-outer (each store one
@@ -82,7 +108,9 @@ __device__ __forceinline__ void for_terms(const TermRec *base, int nt, F &&f) {
 // ---- per-lane node view ----------------------------------------------------
 // kIL (global variant): lb and ub interleaved, [var][lane][2], so a term's
 // two bounds are one 16-B load per lane (one 1-KB wave access)
-template <bool kBitFlags, bool kIL>
+// kColSet: the kernel keeps a changed-column set (FbbtIO::clean_col given);
+// without it every line about the set compiles out
+template <bool kBitFlags, bool kIL, bool kColSet = false>
 struct NodeView {
   double *lb;
   double *ub;
@@ -91,7 +119,55 @@ struct NodeView {
   int stride;        // elements between consecutive variables (same lane)
   int lane;
   const int32_t *rowidx;
+  // Changed-column set of this lane's wave (FbbtIO::clean_col): four LDS
+  // words, bit j = some lane's bounds of column j were stored since the
+  // wave's last column pass.  Kept in LDS and wave-uniform, so it costs no
+  // register across the row loop.  One wave's own words: an elected lane
+  // ORs, every lane loads, lanes 0-3 clear, all with relaxed wavefront-scope
+  // atomics, which is ordered only because one wave's DS instructions
+  // execute in program order.  Memory that several waves share, or a wider
+  // scope, would need real synchronisation.
+  uint32_t *cols;
   static constexpr bool kBits = kBitFlags;
+  static constexpr bool kCols = kBitFlags && kIL && kColSet;
+  // a bound of column j (wave-uniform) was stored by the active lanes
+  __device__ __forceinline__ void mark(int j) const {
+    if constexpr (kCols) {
+      if (lane == rfl(lane))   // one of the storing lanes
+        __hip_atomic_fetch_or(cols + (j >> 5), 1u << (j & 31), __ATOMIC_RELAXED,
+                              __HIP_MEMORY_SCOPE_WAVEFRONT);
+    }
+  }
+  // A fresh node (each lane its own): cc = its clean column, the one column
+  // in which it differs from a box that passed the column loops, or -1: it
+  // may differ in any, and the wave's next pass takes every column.
+  __device__ __forceinline__ void mark_fresh(int cc, int n) const {
+    if constexpr (kCols) {
+      if (cc >= 0 && cc < n) {
+        __hip_atomic_fetch_or(cols + (cc >> 5), 1u << (cc & 31), __ATOMIC_RELAXED,
+                              __HIP_MEMORY_SCOPE_WAVEFRONT);
+      } else {
+#pragma unroll
+        for (int w = 0; w < 4; ++w)
+          __hip_atomic_fetch_or(cols + w, ~0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+      }
+    }
+  }
+  // lanes k < cnt whose column jl is due in this column pass (full wave)
+  __device__ __forceinline__ uint64_t due(int jl, int cnt) const {
+    if constexpr (kCols) {
+      const unsigned w = __hip_atomic_load(cols + ((jl >> 5) & 3), __ATOMIC_RELAXED,
+                                           __HIP_MEMORY_SCOPE_WAVEFRONT);
+      return __ballot(lane < cnt && ((w >> (jl & 31)) & 1u));
+    }
+    return cnt >= kLanes ? ~0ull : (1ull << cnt) - 1ull;
+  }
+  // after the column pass of a wave-sweep (full wave)
+  __device__ __forceinline__ void cols_clear() const {
+    if constexpr (kCols) {
+      __hip_atomic_store(cols + (lane & 3), 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+    }
+  }
   __device__ __forceinline__ double &L(int j) const {
     if constexpr (kIL) return lb[((size_t)j * kLanes + lane) * 2];
     else return lb[j * stride + lane];
@@ -118,6 +194,9 @@ struct NodeView {
     }
   }
 };
+
+// LDS of one wave's changed-column set (NodeView::cols): 128 columns
+constexpr int kColsBytes = 16;
 
 // bounds loaded per batch in the column loops (tightenInts_, checkBounds_,
 // staging, write-out): loads issued together, one memory round trip
@@ -325,11 +404,13 @@ __device__ __forceinline__ void upd_side(const TermRec *base, int nt, V &v,
           if (nb > cur[u] - kETol) nb = cur[u];
           v.change_bflag(t[u]);
           v.L(j) = nb;
+          v.mark(j);
           log.push(s, j, 0, nb);
         } else {
           if (nb < cur[u] + kETol) nb = cur[u];
           v.change_bflag(t[u]);
           v.U(j) = nb;
+          v.mark(j);
           log.push(s, j, 1, nb);
         }
         if (count_int && t[u].isint) s.nintmods++;
@@ -468,12 +549,14 @@ __device__ __forceinline__ void rc_upd_side(RowCache<RC> &c, const TermRec *base
         if (nb > c.u[k] - kETol) nb = c.u[k];
         v.change_bflag(t);
         v.L(t.j) = nb;
+        v.mark(t.j);
         c.l[k] = nb;
         log.push(s, t.j, 0, nb);
       } else {
         if (nb < c.l[k] + kETol) nb = c.l[k];
         v.change_bflag(t);
         v.U(t.j) = nb;
+        v.mark(t.j);
         c.u[k] = nb;
         log.push(s, t.j, 1, nb);
       }
@@ -602,18 +685,32 @@ __device__ __forceinline__ bool tighten_ints(const DevLP &lp, const TermRec *ire
     // the columns are distinct, so the bounds of 8 of them are loaded before
     // any is written: one memory round trip per 8 columns instead of one per
     // column (the compiler cannot prove the stores do not alias later loads)
-    for (int k0 = 0; k0 < cnt; k0 += kBnd) {
+    // Only the columns due in this pass (NodeView::due: all of them without
+    // a column set), in ascending order, which keeps the mod log's order.  A
+    // column not due has bounds that passed this loop unchanged since: it
+    // would push nothing, flag no row and pass the check again.
+    // A kernel without a set walks k0 .. k0 + 7, the code it always had.
+    uint64_t sel = V::kCols ? v.due(ch.j, cnt) : 0ull;
+    int k0 = 0;
+    while (V::kCols ? sel != 0ull : k0 < cnt) {
       double lv[kBnd], uv[kBnd];
+      int kk[kBnd];   // this batch's lanes of ch, -1 = none (kk[0] >= 0)
 #pragma unroll
       for (int e = 0; e < kBnd; ++e) {
-        const int jj = rl(ch.j, k0 + e < cnt ? k0 + e : k0);
+        if constexpr (V::kCols) {
+          kk[e] = sel != 0ull ? (int)__builtin_ctzll(sel) : -1;
+          sel &= sel - 1ull;   // 0 stays 0
+        } else {
+          kk[e] = k0 + e < cnt ? k0 + e : -1;
+        }
+        const int jj = rl(ch.j, kk[e] >= 0 ? kk[e] : kk[0]);
         lv[e] = v.L(jj);
         uv[e] = v.U(jj);
       }
 #pragma unroll
       for (int e = 0; e < kBnd; ++e) {
-      const int k = k0 + e;
-      if (k >= cnt) break;
+      const int k = kk[e];
+      if (k < 0) break;
       const Term1 t{0.0, rlu64(ch.cmask, k), rl(ch.j, k), rl(ch.cs, k), rl(ch.ce, k), 1};
       const int j = t.j;
       const double l = lv[e], u = uv[e];
@@ -636,6 +733,7 @@ __device__ __forceinline__ bool tighten_ints(const DevLP &lp, const TermRec *ire
       }
       bad |= l2 > u2 + kETol;
       }
+      k0 += kBnd;
     }
   }
   return bad;
@@ -651,23 +749,35 @@ __device__ __forceinline__ bool check_bounds_rest(const DevLP &lp, const V &v, b
   for (int c0 = 0; c0 < lp.ncont; c0 += kLanes) {
     const int cnt = lp.ncont - c0 < kLanes ? lp.ncont - c0 : kLanes;
     const int jl = v.lane < cnt ? lp.ccont[c0 + v.lane] : 0;
-    for (int k0 = 0; k0 < cnt; k0 += kBnd) {
+    // as in tighten_ints; a spent slot repeats the batch's last column (an OR)
+    uint64_t sel = V::kCols ? v.due(jl, cnt) : 0ull;
+    int k0 = 0;
+    while (V::kCols ? sel != 0ull : k0 < cnt) {
       double lv[kBnd], uv[kBnd];
+      int k1 = k0;
 #pragma unroll
       for (int e = 0; e < kBnd; ++e) {
-        const int j = rl(jl, k0 + e < cnt ? k0 + e : k0);
+        if constexpr (V::kCols) {
+          if (sel != 0ull) k1 = (int)__builtin_ctzll(sel);
+          sel &= sel - 1ull;   // 0 stays 0
+        } else {
+          k1 = k0 + e < cnt ? k0 + e : k0;
+        }
+        const int j = rl(jl, k1);
         lv[e] = v.L(j);
         uv[e] = v.U(j);
       }
 #pragma unroll
-      for (int e = 0; e < kBnd; ++e)
-        if (k0 + e < cnt) bad |= lv[e] > uv[e] + kETol;
+      for (int e = 0; e < kBnd; ++e) bad |= lv[e] > uv[e] + kETol;
+      k0 += kBnd;
     }
   }
   return bad || lp.cons_bad != 0;
 }
 
-template <bool kLds, bool kBitFlags, bool kTL>
+// kCS: with a changed-column set (io.clean_col given, n <= 128; the bit-flag
+// kernels on the global scratch only)
+template <bool kLds, bool kBitFlags, bool kTL, bool kCS = false>
 __global__ __launch_bounds__(kLanes) void fbbt_linear_kernel(DevLP lp, FbbtIO io) {
   extern __shared__ double lds[];
   const int lane = threadIdx.x;
@@ -683,10 +793,21 @@ __global__ __launch_bounds__(kLanes) void fbbt_linear_kernel(DevLP lp, FbbtIO io
     if (lane < nb && io.order != nullptr) node = io.order[b0 + lane];
   InfRows inf_rows{0u};
 
-  NodeView<kBitFlags, !kLds> v;
+  static_assert(!kCS || (kBitFlags && !kLds), "the column set needs the masks' kernels");
+  NodeView<kBitFlags, !kLds, kCS> v;
   v.lane = lane;
   v.rowidx = lp.rowidx;
   v.bits = 0ull;
+  v.cols = nullptr;
+  if constexpr (kCS) {
+    // the changed-column set (FbbtIO::clean_col): kColsBytes of dynamic LDS
+    // after the staged records (static LDS would not fit under the 160 KiB
+    // the launch asks for)
+    v.cols = reinterpret_cast<uint32_t *>(
+        reinterpret_cast<char *>(lds) +
+        (kTL ? (size_t)m * sizeof(RowRec) + (size_t)lp.nnz * sizeof(TermRec) : 0));
+    v.cols_clear();
+  }
   if constexpr (kLds) {
     v.stride = kLdsStride;
     v.lb = lds;
@@ -740,6 +861,8 @@ __global__ __launch_bounds__(kLanes) void fbbt_linear_kernel(DevLP lp, FbbtIO io
     v.bits = all_rows;
     if constexpr (kMasks)
       if (lane < nb && io.init_mask != nullptr) v.bits &= io.init_mask[node];
+    if constexpr (kCS)
+      if (lane < nb) v.mark_fresh(io.clean_col[node], n);
   } else {
     for (int r = 0; r < m; ++r) v.flag[r * kLanes + lane] = 1;
   }
@@ -813,6 +936,7 @@ __global__ __launch_bounds__(kLanes) void fbbt_linear_kernel(DevLP lp, FbbtIO io
     }
     // both called with the full wave active (v_readlane broadcasts inside)
     const bool bad = check_bounds_rest(lp, v, tighten_ints(lp, lp.irec, v, s, log, go, changed));
+    v.cols_clear();
     if (go) infeas = bad;
   }
   if (live) {
@@ -849,14 +973,14 @@ __global__ __launch_bounds__(kLanes) void fbbt_linear_kernel(DevLP lp, FbbtIO io
 // its own scratch slot and node queue position; no barrier after staging).
 // Three waves per SIMD (168 VGPRs, a few spilled): 524 288 tls4-OA nodes
 // 8.29 -> 7.75 ms with 12 waves per CU (profiles/r04s).
-template <int kWG>
+template <int kWG, bool kCS>
 __global__ __launch_bounds__(kLanes * kWG, 3) void fbbt_linear_persist(DevLP lp,
                                                                                    FbbtIO io) {
   extern __shared__ double lds[];
   const int lane = threadIdx.x & (kLanes - 1);
   const int wave = blockIdx.x * kWG + (int)(threadIdx.x / kLanes);
   const int n = lp.n, m = lp.m;
-  NodeView<true, true> v;
+  NodeView<true, true, kCS> v;
   v.lane = lane;
   v.rowidx = lp.rowidx;
   v.bits = 0ull;
@@ -864,13 +988,19 @@ __global__ __launch_bounds__(kLanes * kWG, 3) void fbbt_linear_persist(DevLP lp,
   v.lb = io.scratch + (size_t)wave * 2 * n * kLanes;
   v.ub = v.lb + (size_t)n * kLanes;
   v.flag = nullptr;
-  // row and term records staged once into LDS
   // row, term, objective and integer-column records staged once into LDS
   RowRec *s_rows = reinterpret_cast<RowRec *>(lds);
   TermRec *s_trec = reinterpret_cast<TermRec *>(reinterpret_cast<char *>(lds) +
                                                 (size_t)m * sizeof(RowRec));
   TermRec *s_orec = s_trec + lp.nnz;
   TermRec *s_irec = s_orec + lp.nobj;
+  // the wave's changed-column set (FbbtIO::clean_col), empty between sweeps:
+  // kColsBytes per wave after the staged records
+  v.cols = nullptr;
+  if constexpr (kCS) {
+    v.cols = reinterpret_cast<uint32_t *>(s_irec + lp.nint) + 4 * (threadIdx.x / kLanes);
+    v.cols_clear();
+  }
   {
     const uint4 *src = reinterpret_cast<const uint4 *>(lp.rows);
     uint4 *dst = reinterpret_cast<uint4 *>(s_rows);
@@ -890,7 +1020,6 @@ __global__ __launch_bounds__(kLanes * kWG, 3) void fbbt_linear_persist(DevLP lp,
   const TermRec *trec = s_trec;
   const RowRec *rows = s_rows;
   const uint64_t all_rows = m >= 64 ? ~0ull : ((1ull << m) - 1ull);
-  const uint64_t lt_mask = lane == 0 ? 0ull : (~0ull >> (64 - lane));
 
   int node = -1;
   bool has = false, changed = false, infeas = false, exhausted = false;
@@ -900,7 +1029,9 @@ __global__ __launch_bounds__(kLanes * kWG, 3) void fbbt_linear_persist(DevLP lp,
   unsigned it_st = 1u;
   NodeState s{0, 0u};
   ModLog log{nullptr, nullptr, nullptr, io.mod_cap};
+  KSTAMP_DECL
   while (true) {
+    KSTAMP(5);
     bool go = has && changed && (it_st & 15u) <= 10u &&
               ((it_st & 15u) <= 2u || s.nintmods > 0u) && !infeas;
     // retire: nodes whose sweep loop ended (checked at the sweep boundary,
@@ -916,6 +1047,7 @@ __global__ __launch_bounds__(kLanes * kWG, 3) void fbbt_linear_persist(DevLP lp,
         has = false;
       }
     }
+    KSTAMP(4);
     // refill idle lanes from the queue (one atomic per wave)
     if (!exhausted) {
       const uint64_t idle = __ballot(!has);
@@ -926,7 +1058,10 @@ __global__ __launch_bounds__(kLanes * kWG, 3) void fbbt_linear_persist(DevLP lp,
         base = __shfl(base, (int)__builtin_ctzll(idle), kLanes);
         if (base + cnt >= io.batch) exhausted = true;
         if (!has) {
-          const int my = base + __popcll(idle & lt_mask);
+          // + the idle lanes below this one (v_mbcnt: no per-lane mask to keep)
+          const int my = base + (int)__builtin_amdgcn_mbcnt_hi(
+                                    (unsigned)(idle >> 32),
+                                    __builtin_amdgcn_mbcnt_lo((unsigned)idle, 0u));
           if (my < io.batch) {
             node = io.order != nullptr ? io.order[my] : my;
             has = true;
@@ -934,6 +1069,7 @@ __global__ __launch_bounds__(kLanes * kWG, 3) void fbbt_linear_persist(DevLP lp,
             // simplePresolve: every constraint's BFlag set (:1618-1622), less
             // the rows the caller knows to be clean
             v.bits = io.init_mask != nullptr ? io.init_mask[node] & all_rows : all_rows;
+            if constexpr (kCS) v.mark_fresh(io.clean_col[node], n);
             s.nmods = 0;
             s.nintmods = 0u;
             changed = true;
@@ -951,6 +1087,7 @@ __global__ __launch_bounds__(kLanes * kWG, 3) void fbbt_linear_persist(DevLP lp,
         }
       }
     }
+    KSTAMP(3);
     if (!__any(go)) {
       if (exhausted || !__any(has)) break;
       continue;
@@ -995,34 +1132,52 @@ __global__ __launch_bounds__(kLanes * kWG, 3) void fbbt_linear_persist(DevLP lp,
         }
       }
     }
+    KSTAMP(0);
     if (go && io.has_inc && lp.nobj > 0) {
       if (lp.nobj <= 16) rc_bnds_from_obj<16>(lp.nobj, s_orec, v, s, log, io.inc_ub, changed);
       else bnds_from_obj(s_orec, lp.nobj, v, s, log, io.inc_ub, changed);
     }
+    KSTAMP(1);
     const bool bad = check_bounds_rest(lp, v, tighten_ints(lp, s_irec, v, s, log, go, changed));
+    v.cols_clear();
     if (go) infeas = bad;
+    KSTAMP(2);
   }
+  KSTAMP_FLUSH
 }
 
-template <bool kLds, bool kBits, bool kTL>
+template <bool kLds, bool kBits, bool kTL, bool kCS = false>
 hipError_t launch_variant(const DevLP &lp, const FbbtIO &io, size_t lds, hipStream_t stream) {
   const int waves = (io.batch + io.npw - 1) / io.npw;
   {
     static bool attr_set = false;  // dynamic LDS above 64 KiB must be opted in
     if (!attr_set) {
-      hipError_t e = hipFuncSetAttribute((const void *)fbbt_linear_kernel<kLds, kBits, kTL>,
+      hipError_t e = hipFuncSetAttribute((const void *)fbbt_linear_kernel<kLds, kBits, kTL, kCS>,
                                          hipFuncAttributeMaxDynamicSharedMemorySize,
                                          160 * 1024);
       if (e != hipSuccess) return e;
       attr_set = true;
     }
   }
-  hipLaunchKernelGGL((fbbt_linear_kernel<kLds, kBits, kTL>), dim3(waves), dim3(kLanes),
+  hipLaunchKernelGGL((fbbt_linear_kernel<kLds, kBits, kTL, kCS>), dim3(waves), dim3(kLanes),
                      lds, stream, lp, io);
   return hipGetLastError();
 }
 
 }  // namespace
+
+#ifdef MGPU_K1_STAMPS
+extern "C" int mgpu_debug_k1_stamps(unsigned long long *out, int reset) {
+  if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_k1_stamps), sizeof(unsigned long long) * 8) !=
+      hipSuccess)
+    return -1;
+  if (reset) {
+    const unsigned long long z[8] = {0};
+    if (hipMemcpyToSymbol(HIP_SYMBOL(g_k1_stamps), z, sizeof z) != hipSuccess) return -1;
+  }
+  return 0;
+}
+#endif
 
 size_t fbbt_persist_lds(const DevLP &lp) {
   return (size_t)lp.m * sizeof(RowRec) + (size_t)(lp.nnz + lp.nobj + lp.nint) * sizeof(TermRec);
@@ -1038,6 +1193,9 @@ hipError_t launch_fbbt_linear(const DevLP &lp, const FbbtIO &io, int variant,
   const size_t lds = fbbt_lds_bytes(lp.n, lp.m);
   const bool use_lds = variant == 1 || (variant == 0 && lds <= 160 * 1024);
   const bool bits = lp.m <= 64;
+  // a changed-column set: its own instantiations, so that a launch without
+  // the hint runs the code it ran before the set existed
+  const bool cs = bits && io.clean_col != nullptr && lp.n <= 128;
   // records table next to the bounds (LDS variant) or alone (global variant)
   const size_t tab = (size_t)lp.m * sizeof(RowRec) + (size_t)lp.nnz * sizeof(TermRec);
   static const bool no_tl = getenv("MGPU_FBBT_NOTL") != nullptr;  // A/B switch
@@ -1055,22 +1213,27 @@ hipError_t launch_fbbt_linear(const DevLP &lp, const FbbtIO &io, int variant,
     static const int wg = getenv("MGPU_FBBT_WG") ? atoi(getenv("MGPU_FBBT_WG")) : 4;
     static bool attr_set = false;
     if (!attr_set) {
-      for (const void *f : {(const void *)fbbt_linear_persist<1>,
-                            (const void *)fbbt_linear_persist<4>}) {
+      for (const void *f : {(const void *)fbbt_linear_persist<1, false>,
+                            (const void *)fbbt_linear_persist<4, false>,
+                            (const void *)fbbt_linear_persist<1, true>,
+                            (const void *)fbbt_linear_persist<4, true>}) {
         hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize,
                                            160 * 1024);
         if (e != hipSuccess) return e;
       }
       attr_set = true;
     }
-    if (wg == 1)
-      hipLaunchKernelGGL(fbbt_linear_persist<1>, dim3(io.npw), dim3(kLanes), ptab, stream, lp, io);
-    else
-      hipLaunchKernelGGL(fbbt_linear_persist<4>, dim3((io.npw + 3) / 4), dim3(4 * kLanes), ptab,
-                         stream, lp, io);
+    const dim3 grid(wg == 1 ? io.npw : (io.npw + 3) / 4), block(wg == 1 ? kLanes : 4 * kLanes);
+    void (*kern)(DevLP, FbbtIO) =
+        cs ? (wg == 1 ? fbbt_linear_persist<1, true> : fbbt_linear_persist<4, true>)
+           : (wg == 1 ? fbbt_linear_persist<1, false> : fbbt_linear_persist<4, false>);
+    hipLaunchKernelGGL(kern, grid, block, ptab + (cs ? (wg == 1 ? 1 : 4) * kColsBytes : 0), stream,
+                       lp, io);
     return hipGetLastError();
   }
   const bool tl = !no_tl && bits && tab <= 64 * 1024;
+  if (cs && tl) return launch_variant<false, true, true, true>(lp, io, tab + kColsBytes, stream);
+  if (cs) return launch_variant<false, true, false, true>(lp, io, kColsBytes, stream);
   if (tl) return launch_variant<false, true, true>(lp, io, tab, stream);
   return bits ? launch_variant<false, true, false>(lp, io, 0, stream)
               : launch_variant<false, false, false>(lp, io, 0, stream);

@@ -341,6 +341,13 @@ struct FbbtIO {
   const uint64_t *init_mask;    // [B] or null: all rows
   uint64_t *carry_out;          // [B] or null: not written
   const int32_t *order;         // [B] or null: identity
+  // Clean columns (the same kernels, and n <= 128).  clean_col[b] = j >= 0
+  // promises that node b's box is a feasible K1 output (every integer column
+  // integral or infinite, every column past checkBounds_) in which only
+  // column j's bounds moved since; -1 promises nothing.  tightenInts_ and
+  // checkBounds_ then take only the columns stored since the wave's last
+  // pass, plus j: a column not stored since it passed would pass unchanged.
+  const int32_t *clean_col;     // [B] or null: nothing known
 };
 
 constexpr int kLanes = 64;      // wave64: one node per lane

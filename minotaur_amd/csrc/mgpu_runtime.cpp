@@ -434,6 +434,16 @@ int mgpu_fbbt_masked_dev(mgpu_ctx *c, int batch, const double *lb_in, const doub
                          int32_t *nmods, int mod_cap, int32_t *mod_var, int32_t *mod_lu,
                          double *mod_val, const uint64_t *init_mask, uint64_t *carry_out,
                          const int32_t *order) {
+  return mgpu_fbbt_cols_dev(c, batch, lb_in, ub_in, incumbent, lb_out, ub_out, infeas, nmods,
+                            mod_cap, mod_var, mod_lu, mod_val, init_mask, carry_out, order,
+                            nullptr);
+}
+
+int mgpu_fbbt_cols_dev(mgpu_ctx *c, int batch, const double *lb_in, const double *ub_in,
+                       double incumbent, double *lb_out, double *ub_out, int32_t *infeas,
+                       int32_t *nmods, int mod_cap, int32_t *mod_var, int32_t *mod_lu,
+                       double *mod_val, const uint64_t *init_mask, uint64_t *carry_out,
+                       const int32_t *order, const int32_t *clean_col) {
   if (!c) return MGPU_ERR_ARG;
   if (!c->loaded) return fail(c, MGPU_ERR_STATE, "mgpu_fbbt: no problem loaded");
   if (batch < 0 || (batch > 0 && (!lb_in || !ub_in || !lb_out || !ub_out || !infeas || !nmods)))
@@ -472,6 +482,7 @@ int mgpu_fbbt_masked_dev(mgpu_ctx *c, int batch, const double *lb_in, const doub
     io.init_mask = init_mask;
     io.carry_out = carry_out;
     io.order = order;
+    io.clean_col = clean_col;   // the kernels take it for n <= 128
   } else if (carry_out != nullptr) {
     HIPCHK(c, hipMemsetAsync(carry_out, 0xFF, (size_t)batch * sizeof(uint64_t), c->stream));
   }

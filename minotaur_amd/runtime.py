@@ -48,7 +48,7 @@ EXPORTS = [
     'mgpu_alltoall_rows_dev', 'mgpu_lb_deal', 'mgpu_bnb_rebalance', 'mgpu_alloc_stats',
     'mgpu_bnb_growth', 'mgpu_set_sb_chain', 'mgpu_glob_brancher', 'mgpu_glob_lp_log',
     'mgpu_node_serialize', 'mgpu_node_deserialize',
-    'mgpu_fbbt_masked_dev', 'mgpu_bnb_fbbt_carry',
+    'mgpu_fbbt_masked_dev', 'mgpu_fbbt_cols_dev', 'mgpu_bnb_fbbt_carry',
 ]
 
 COMM_ID_BYTES = 128            # MGPU_COMM_ID_BYTES
@@ -127,6 +127,7 @@ def load_library():
     lib.mgpu_fbbt_dev.argtypes = [_P, _I, _P, _P, _D, _P, _P, _P, _P, _I, _P, _P, _P]
     lib.mgpu_fbbt_masked_dev.argtypes = [_P, _I, _P, _P, _D, _P, _P, _P, _P, _I, _P, _P, _P,
                                          _P, _P, _P]
+    lib.mgpu_fbbt_cols_dev.argtypes = lib.mgpu_fbbt_masked_dev.argtypes + [_P]
     lib.mgpu_bnb_fbbt_carry.argtypes = [_P, _I]
     lib.mgpu_set_fbbt_variant.argtypes = [_P, _I]
     lib.mgpu_set_lp_variant.argtypes = [_P, _I]
@@ -549,6 +550,16 @@ class Context:
             _dp(infeasible), _dp(nmods), 0, None, None, None, _dp(init_mask), _dp(carry_out),
             _dp(order)), 'mgpu_fbbt_masked_dev')
 
+    def fbbt_cols_dev(self, lb, ub, lb_out, ub_out, infeasible, nmods, incumbent=math.inf,
+                      init_mask=None, carry_out=None, order=None, clean_col=None):
+        """fbbt_masked_dev with clean columns (mgpu_fbbt_cols_dev): clean_col
+        int32 [B], the one column moved since the box left K1 feasible, or -1."""
+        B = int(lb.shape[0])
+        self._chk(self.lib.mgpu_fbbt_cols_dev(
+            self.h, B, _dp(lb), _dp(ub), float(incumbent), _dp(lb_out), _dp(ub_out),
+            _dp(infeasible), _dp(nmods), 0, None, None, None, _dp(init_mask), _dp(carry_out),
+            _dp(order), _dp(clean_col)), 'mgpu_fbbt_cols_dev')
+
     # -- LP ------------------------------------------------------------------
     def lp_solve(self, lb, ub, ws=None, skip=None, iter_limit=0, want_x=False,
                  want_ws=False) -> LpOut:
@@ -776,7 +787,8 @@ class Context:
 
     def bnb_fbbt_carry(self, mode):
         """Next tree's clean-row masks (mgpu_bnb_fbbt_carry): 0 off, 1 masks,
-        2 masks + nodes grouped by branching variable (default)."""
+        2 masks + nodes grouped by branching variable, 3 (default) also the
+        branching variable as each child's clean column."""
         self._chk(self.lib.mgpu_bnb_fbbt_carry(self.h, int(mode)), 'mgpu_bnb_fbbt_carry')
 
     def bnb_brancher(self, kind):
