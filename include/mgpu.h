@@ -813,13 +813,19 @@ int mgpu_glob_lp_log(mgpu_ctx *ctx, int cap, int32_t *status, double *value, int
  * Replaces BqpdEngine::solve (src/interfaces/BqpdEngine.cpp:449-534) on the
  * QP relaxation QPDRelaxer builds (examples/QPDRelaxer.cpp:56-126):
  *     min 1/2 x'Qx + c'x + k  s.t.  A x = b,  lb <= x <= ub   (node box)
- * Q dense symmetric PSD [n][n] (row-major), A dense [m][n] (m <= 64).
+ * Q dense [n][n] (row-major, PSD; the load takes its symmetric part), A dense
+ * [m][n].  mgpu_load_qp accepts n <= MGPU_QP_MAX_N and 0 <= m <=
+ * MGPU_QP_MAX_M and refuses any other shape with MGPU_ERR_ARG: past
+ * MGPU_QP_MAX_N columns (1248 padded to 16) the right-looking factor
+ * kernel's panel does not fit the 160 KiB of LDS, so no kernel could run it.
  * mgpu_qp_solve[_dev]: one primal-dual interior point solve per node box
  * ([batch][n] lb/ub, finite), Mehrotra predictor-corrector, Newton systems
  * through K = Q + D = L L' (MFMA blocked Cholesky) and M = A K^-1 A'.
  *   status[b]: 0 optimal (residuals <= 1e-9 (1 + |b|, |c|), mu <= 1e-10),
  *              6 iteration limit (maxit, default 80);
  *   obj[b] = 1/2 x'Qx + c'x + k;  iters[b];  x [batch][n] optional. */
+#define MGPU_QP_MAX_N 1248
+#define MGPU_QP_MAX_M 64
 int mgpu_load_qp(mgpu_ctx *ctx, int n, int m, const double *Q, const double *c, double k,
                  const double *A, const double *b);
 int mgpu_qp_solve(mgpu_ctx *ctx, int batch, const double *lb, const double *ub, int maxit,
@@ -827,6 +833,13 @@ int mgpu_qp_solve(mgpu_ctx *ctx, int batch, const double *lb, const double *ub, 
 int mgpu_qp_solve_dev(mgpu_ctx *ctx, int batch, const double *d_lb, const double *d_ub,
                       int maxit, int32_t *d_status, double *d_obj, int32_t *d_iters,
                       double *d_x);
+/* Diagnostic: which kernels the loaded QP's shape takes per iteration.
+ *   flags bit 0   left-looking factor (qp_potrf_ll; 0: qp_potrf)
+ *         bit 1   W resident in LDS (qp_trsm_syrk_lds; 0: qp_trsm_syrk)
+ *         bits 2-3  columns per thread of the step kernel: 0 / 1 / 2 for
+ *                   qp_step<2> / <4> / <8>
+ * Not a reference interface: the tests pin each variant's coverage with it. */
+int mgpu_qp_plan(mgpu_ctx *ctx, int *flags);
 
 /* ---- quadratic node FBBT (K2) ------------------------------------------
  * Replaces QuadHandler::presolveNode (src/base/QuadHandler.cpp:1204-1269)

@@ -38,6 +38,16 @@ struct QpWork {
   double *obj;
 };
 
+// Which kernels one interior-point iteration takes at a padded shape: the
+// one place the LDS budgets of qp_kkt.hip's variants are weighed.
+struct QpPlan {
+  bool ll;   // qp_potrf_ll (left-looking Cholesky); else qp_potrf
+  bool wl;   // qp_trsm_syrk_lds (W resident in LDS); else qp_trsm_syrk
+  int J;     // columns per thread of qp_step<J>: 2, 4 or 8
+  bool ok;   // every chosen kernel can be launched; mgpu_load_qp refuses the rest
+};
+QpPlan qp_plan(int np, int mp, int m);
+
 size_t qp_step_lds(int np, int mp, int m);
 hipError_t launch_qp_init(const DevQP &q, const QpWork &w, hipStream_t s);
 // ev (optional): four events recorded before the factor kernel, after it,

@@ -991,6 +991,30 @@ size_t qp_step_lds(int np, int mp, int m) {
   return sizeof(double) * ((size_t)2 * np + mp + (size_t)m * (m + 1) / 2 + 2 * 204 + 4 * 272);
 }
 
+namespace {
+// the opt-in dynamic LDS every factor / step kernel is given below
+constexpr size_t kLdsMax = 160 * 1024;
+// qp_potrf: the diagonal tile and the column block's panel of np / 16 tiles
+size_t potrf_rl_lds(int np) { return sizeof(double) * (16 * 17 + (size_t)(np / 16) * 256); }
+// qp_trsm_syrk: the diagonal tile and one block row of W
+size_t trsm_rl_lds(int mp) { return sizeof(double) * (16 * 17 + (size_t)16 * mp); }
+}  // namespace
+
+QpPlan qp_plan(int np, int mp, int m) {
+  static const bool rl = getenv("MGPU_QP_RIGHT_LOOKING") != nullptr;   // A/B switch
+  QpPlan p;
+  // left-looking factorization while its column block and the two [np]
+  // vectors fit the LDS (np <= 1120)
+  p.ll = !rl && potrf_ll_lds(np) <= kLdsMax;
+  // W resident in LDS when it fits (np (mp + 1) + 272 <= 20 480 doubles)
+  p.wl = p.ll && trsm_lds_bytes(np, mp) <= kLdsMax;
+  p.J = np <= 2 * kT ? 2 : np <= 4 * kT ? 4 : 8;
+  // qp_potrf's panel is what ends first: np <= 1248
+  p.ok = np <= 8 * kT && (p.ll || potrf_rl_lds(np) <= kLdsMax) &&
+         (p.wl || trsm_rl_lds(mp) <= kLdsMax) && qp_step_lds(np, mp, m) <= kLdsMax;
+  return p;
+}
+
 hipError_t launch_qp_init(const DevQP &q, const QpWork &w, hipStream_t s) {
   hipLaunchKernelGGL(qp_init, dim3(w.B), dim3(kT), 0, s, q, w);
   return hipGetLastError();
@@ -1003,50 +1027,44 @@ hipError_t launch_qp_iteration(const DevQP &q, const QpWork &w, hipStream_t s, h
     for (const void *f : {(const void *)qp_step<2>, (const void *)qp_step<4>,
                           (const void *)qp_step<8>})
       if (e == hipSuccess)
-        e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax);
     if (e == hipSuccess)
       e = hipFuncSetAttribute((const void *)qp_potrf,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax);
     if (e == hipSuccess)
       e = hipFuncSetAttribute((const void *)qp_potrf_ll,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax);
     if (e == hipSuccess)
       e = hipFuncSetAttribute((const void *)qp_trsm_syrk_lds,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax);
     if (e != hipSuccess) return e;
     attr = true;
   }
+  const QpPlan p = qp_plan(q.np, q.mp, q.m);
+  if (!p.ok) return hipErrorInvalidValue;   // mgpu_load_qp refuses these shapes
   const size_t lds_prep = sizeof(double) * (size_t)(q.np + q.mp);
-  const size_t lds_potrf = sizeof(double) * (16 * 17 + (size_t)(q.np / 16) * 256);
-  const size_t lds_trsm = sizeof(double) * (16 * 17 + (size_t)16 * q.mp);
-  // left-looking factorization while its row panel fits the LDS (n <= ~580)
-  static const bool rl = getenv("MGPU_QP_RIGHT_LOOKING") != nullptr;   // A/B switch
-  const bool ll = !rl && potrf_ll_lds(q.np) <= 160 * 1024;
-  // W resident in LDS when it fits (n * (m + 1) <= ~20 000)
-  const bool wl = ll && trsm_lds_bytes(q.np, q.mp) <= 160 * 1024;
-  hipLaunchKernelGGL(qp_prep, dim3(w.B), dim3(kT), lds_prep, s, q, w, (ll ? 0 : 1) | (wl ? 0 : 2));
+  hipLaunchKernelGGL(qp_prep, dim3(w.B), dim3(kT), lds_prep, s, q, w,
+                     (p.ll ? 0 : 1) | (p.wl ? 0 : 2));
   if (ev) (void)hipEventRecord(ev[0], s);
-  if (ll)
+  if (p.ll)
     hipLaunchKernelGGL(qp_potrf_ll, dim3(w.B), dim3(kPT), potrf_ll_lds(q.np), s, q, w);
   else
-    hipLaunchKernelGGL(qp_potrf, dim3(w.B), dim3(kT), lds_potrf, s, w, q.np);
+    hipLaunchKernelGGL(qp_potrf, dim3(w.B), dim3(kT), potrf_rl_lds(q.np), s, w, q.np);
   if (ev) (void)hipEventRecord(ev[1], s);
-  if (wl)
+  if (p.wl)
     hipLaunchKernelGGL(qp_trsm_syrk_lds, dim3(w.B), dim3(kPT), trsm_lds_bytes(q.np, q.mp), s, q,
                        w);
   else
-    hipLaunchKernelGGL(qp_trsm_syrk, dim3(w.B), dim3(kT), lds_trsm, s, w, q.np, q.mp);
+    hipLaunchKernelGGL(qp_trsm_syrk, dim3(w.B), dim3(kT), trsm_rl_lds(q.mp), s, w, q.np, q.mp);
   if (ev) (void)hipEventRecord(ev[2], s);
   // the step's per-column registers: J columns per thread
   const size_t lstep = qp_step_lds(q.np, q.mp, q.m);
-  if (q.np <= 2 * kT)
+  if (p.J == 2)
     hipLaunchKernelGGL(qp_step<2>, dim3(w.B), dim3(kT), lstep, s, q, w);
-  else if (q.np <= 4 * kT)
+  else if (p.J == 4)
     hipLaunchKernelGGL(qp_step<4>, dim3(w.B), dim3(kT), lstep, s, q, w);
-  else if (q.np <= 8 * kT)
-    hipLaunchKernelGGL(qp_step<8>, dim3(w.B), dim3(kT), lstep, s, q, w);
   else
-    return hipErrorInvalidValue;   // n > 2048: mgpu_load_qp refuses it
+    hipLaunchKernelGGL(qp_step<8>, dim3(w.B), dim3(kT), lstep, s, q, w);
   if (ev) (void)hipEventRecord(ev[3], s);
   return hipGetLastError();
 }

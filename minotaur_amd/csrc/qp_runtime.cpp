@@ -12,6 +12,7 @@
 
 struct QpState {
   DevQP dq{};
+  QpPlan plan{};
   int n = 0, m = 0;
   DevBuf Q, c, A, AT, b;
   DevBuf l, u, x, zl, zu, y, rd, rp, K, W, WT, M, done, iters, status, obj;
@@ -194,15 +195,20 @@ extern "C" {
 int mgpu_load_qp(mgpu_ctx *c, int n, int m, const double *Q, const double *cvec, double k,
                  const double *A, const double *b) {
   if (!c) return MGPU_ERR_ARG;
-  if (n <= 0 || n > 2048 || m < 0 || m > 64 || !Q || !cvec || (m > 0 && (!A || !b)))
-    return fail(c, MGPU_ERR_ARG, "mgpu_load_qp: bad argument (n <= 2048 columns, m <= 64 rows "
-                "supported)");
+  // a shape is accepted when every kernel of its plan can be launched: past
+  // MGPU_QP_MAX_N columns qp_potrf's panel no longer fits the LDS
+  const bool sized = n > 0 && n <= (1 << 20) && m >= 0 && m <= MGPU_QP_MAX_M;
+  const int np = sized ? (n + 15) / 16 * 16 : 0, mp = sized && m > 0 ? (m + 15) / 16 * 16 : 16;
+  const QpPlan plan = sized ? qp_plan(np, mp, m) : QpPlan{};
+  if (!plan.ok || !Q || !cvec || (m > 0 && (!A || !b)))
+    return fail(c, MGPU_ERR_ARG, "mgpu_load_qp: bad argument (n <= %d columns, m <= %d rows "
+                "supported)", MGPU_QP_MAX_N, MGPU_QP_MAX_M);
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   qp_state_free(c);
   QpState *s = new QpState();
   c->qp = s;
-  const int np = (n + 15) / 16 * 16, mp = m > 0 ? (m + 15) / 16 * 16 : 16;
+  s->plan = plan;
   std::vector<double> hQ((size_t)np * np, 0.0), hc(np, 0.0), hA((size_t)mp * np, 0.0),
       hAT((size_t)np * mp, 0.0), hb(mp, 0.0);
   double cmax = 0.0, bmax = 0.0;
@@ -240,6 +246,15 @@ int mgpu_load_qp(mgpu_ctx *c, int n, int m, const double *Q, const double *cvec,
   d.k = k;
   d.tp = 1e-9 * (1.0 + bmax);  // oracle/qp_ipm.py TOL_P, TOL_D
   d.td = 1e-9 * (1.0 + cmax);
+  return MGPU_OK;
+}
+
+int mgpu_qp_plan(mgpu_ctx *c, int *flags) {
+  if (!c) return MGPU_ERR_ARG;
+  if (!c->qp) return fail(c, MGPU_ERR_STATE, "mgpu_qp_plan: no QP loaded");
+  if (!flags) return fail(c, MGPU_ERR_ARG, "mgpu_qp_plan: bad argument");
+  const QpPlan &p = c->qp->plan;
+  *flags = (p.ll ? 1 : 0) | (p.wl ? 2 : 0) | ((p.J == 2 ? 0 : p.J == 4 ? 1 : 2) << 2);
   return MGPU_OK;
 }
 

@@ -24,6 +24,8 @@ LP_PFI_BIG = 48  # MGPU_LP_PFI_BIG: the largest cap (the 48-eta build)
 LP_PFI_WIDE_MAX = 32  # MGPU_LP_PFI_WIDE_MAX: K3PW eta-file cap
 PATH_MAX = 32  # MGPU_PATH_MAX: columns per basis warm start
 PATH_INHERIT = 32  # the batched tree's largest basis difference handed to children (warm mode 2)
+QP_MAX_N = 1248  # MGPU_QP_MAX_N: the most columns mgpu_load_qp accepts
+QP_MAX_M = 64  # MGPU_QP_MAX_M: the most rows
 
 # Every entry point declared in include/mgpu.h (checked by the CPU tests).
 EXPORTS = [
@@ -37,6 +39,7 @@ EXPORTS = [
     'mgpu_bnb_round', 'mgpu_bnb_best', 'mgpu_bnb_shard', 'mgpu_bnb_config', 'mgpu_bnb_export',
     'mgpu_bnb_import', 'mgpu_strong_branch',
     'mgpu_strong_branch_dev', 'mgpu_load_qp', 'mgpu_qp_solve', 'mgpu_qp_solve_dev',
+    'mgpu_qp_plan',
     'mgpu_set_node_rows', 'mgpu_lp_solve_rows', 'mgpu_lp_solve_rows_dev', 'mgpu_bnb_brancher',
     'mgpu_bnb_relaxation',
     'mgpu_lp_refactor', 'mgpu_set_lp_pfi_wide', 'mgpu_lp_pfi_cap', 'mgpu_lp_solve_path',
@@ -188,6 +191,7 @@ def load_library():
     lib.mgpu_load_qp.argtypes = [_P, _I, _I, _P, _P, _D, _P, _P]
     lib.mgpu_qp_solve.argtypes = [_P, _I, _P, _P, _I, _P, _P, _P, _P]
     lib.mgpu_qp_solve_dev.argtypes = [_P, _I, _P, _P, _I, _P, _P, _P, _P]
+    lib.mgpu_qp_plan.argtypes = [_P, ctypes.POINTER(_I)]
     lib.mgpu_set_node_rows.argtypes = [_P, _I, _I, _P, _P, _I, _P, _P, _P]
     lib.mgpu_lp_refactor.argtypes = [_P] + [_P] * 7
     lib.mgpu_lp_solve_rows.argtypes = [_P, _I] + [_P] * 6 + [_I, _I] + [_P] * 5
@@ -852,6 +856,13 @@ class Context:
         self._chk(self.lib.mgpu_load_qp(self.h, qp.n, qp.m, _hp(Q), _hp(c), float(qp.k),
                                         _hp(A), _hp(b)), 'mgpu_load_qp')
         self.qp = qp
+
+    def qp_plan(self):
+        """mgpu_qp_plan: (ll, wl, J) of the loaded QP's shape: left-looking
+        factor kernel, W resident in LDS, columns per thread of qp_step."""
+        f = ctypes.c_int(0)
+        self._chk(self.lib.mgpu_qp_plan(self.h, ctypes.byref(f)), 'mgpu_qp_plan')
+        return f.value & 1, (f.value >> 1) & 1, 2 << ((f.value >> 2) & 3)
 
     def qp_solve(self, lb, ub, maxit=0, want_x=True):
         lb = _np(lb, np.float64)

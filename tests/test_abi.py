@@ -70,6 +70,16 @@ def test_pfi_cap_matches_header():
     assert m and int(m.group(1)) == runtime.PATH_MAX == oracle.PATH_MAX
 
 
+def test_qp_limits_match_header():
+    """runtime.QP_MAX_N / QP_MAX_M are the header's limits of mgpu_load_qp
+    (that the library refuses exactly past them: tests/test_qp_shapes_gpu.py)."""
+    hdr = open(os.path.join(ROOT, 'include', 'mgpu.h')).read()
+    m = re.search(r'#define MGPU_QP_MAX_N (\d+)', hdr)
+    assert m and int(m.group(1)) == runtime.QP_MAX_N
+    m = re.search(r'#define MGPU_QP_MAX_M (\d+)', hdr)
+    assert m and int(m.group(1)) == runtime.QP_MAX_M
+
+
 def test_reference_libraries_coexist_in_one_process():
     """The two test libraries that carry the reference objects (oracle/_ref:
     libref_fbbt.so and the integration library, loaded RTLD_GLOBAL by the
