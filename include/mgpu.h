@@ -894,6 +894,14 @@ int mgpu_quad_fbbt_dev(mgpu_ctx *ctx, int batch, const double *d_lb_in, const do
                        double *d_lb_out, double *d_ub_out, double *d_rows_out,
                        int32_t *d_infeas, int32_t *d_nmods, int mod_cap, int32_t *d_mod_kind,
                        int32_t *d_mod_idx, double *d_mod_v1, double *d_mod_v2);
+/* Diagnostic: where the loaded problem's node state lives under the current
+ * mgpu_set_fbbt_variant setting.
+ *   variant    1 LDS, 2 global scratch; 0 when the setting is refused (LDS
+ *              forced and lds_bytes > 160 KiB: mgpu_quad_fbbt then fails).
+ *              Auto takes LDS while lds_bytes <= 40 KiB, else scratch.
+ *   lds_bytes  (2 nv + 2 maxt) * 520, maxt the longest tightenQuad_ term list
+ * Not a reference interface: the tests pin each variant's coverage with it. */
+int mgpu_quad_plan(mgpu_ctx *ctx, int *variant, long long *lds_bytes);
 
 /* Device-side timing of the last launch of the named kernel family
  * ("fbbt", "lp", "quad", "qp", "refactor" = K3R of the last

@@ -407,5 +407,8 @@ struct QuadIO {
 hipError_t launch_quad_fbbt(const DevQuad &q, const QuadIO &io, bool use_lds,
                             hipStream_t stream);
 size_t quad_lds_bytes(const DevQuad &q);
+// Where K2's node state lives: 1 LDS, 2 global scratch, 0 refused (LDS asked
+// for and it does not fit).  requested: mgpu_set_fbbt_variant's value.
+int quad_variant(const DevQuad &q, int requested);
 
 }  // namespace mgpu

@@ -588,17 +588,27 @@ size_t quad_lds_bytes(const DevQuad &q) {
   return (size_t)(2 * q.nv + 2 * q.maxt) * kLdsStride * sizeof(double);
 }
 
+constexpr size_t kQuadLdsAuto = 40 * 1024;  // auto: LDS while several waves fit per CU
+constexpr size_t kQuadLdsMax = 160 * 1024;  // the CU's LDS
+
+int quad_variant(const DevQuad &q, int requested) {
+  const size_t lds = quad_lds_bytes(q);
+  if (requested == 1) return lds <= kQuadLdsMax ? 1 : 0;
+  if (requested == 2) return 2;
+  return lds <= kQuadLdsAuto ? 1 : 2;  // 0 auto (3, 4: K1 only)
+}
+
 hipError_t launch_quad_fbbt(const DevQuad &q, const QuadIO &io, bool use_lds,
                             hipStream_t stream) {
   if (io.batch <= 0) return hipSuccess;
   const int waves = (io.batch + kLanes - 1) / kLanes;
   const size_t lds = quad_lds_bytes(q);
   if (use_lds) {
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
+    if (lds > kQuadLdsMax) return hipErrorInvalidValue;
     static bool attr_set = false;  // dynamic LDS above 64 KiB must be opted in
     if (!attr_set) {
       hipError_t e = hipFuncSetAttribute((const void *)quad_fbbt_kernel<true>,
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, kQuadLdsMax);
       if (e != hipSuccess) return e;
       attr_set = true;
     }

@@ -266,6 +266,15 @@ int mgpu_quad_rows(mgpu_ctx *c, const double *lb, const double *ub, double *rows
   return MGPU_OK;
 }
 
+int mgpu_quad_plan(mgpu_ctx *c, int *variant, long long *lds_bytes) {
+  if (!c) return MGPU_ERR_ARG;
+  if (!c->quad) return fail(c, MGPU_ERR_STATE, "mgpu_quad_plan: no quadratic problem loaded");
+  if (!variant || !lds_bytes) return fail(c, MGPU_ERR_ARG, "mgpu_quad_plan: bad argument");
+  *variant = quad_variant(c->quad->dq, c->fbbt_variant);
+  *lds_bytes = (long long)quad_lds_bytes(c->quad->dq);
+  return MGPU_OK;
+}
+
 int mgpu_quad_fbbt_dev(mgpu_ctx *c, int batch, const double *lb_in, const double *ub_in,
                        double incumbent, int qt, const double *rows_in, int rows_shared,
                        double *lb_out, double *ub_out, double *rows_out, int32_t *infeas,
@@ -303,11 +312,10 @@ int mgpu_quad_fbbt_dev(mgpu_ctx *c, int batch, const double *lb_in, const double
   io.best = incumbent;
   // Variant (mgpu_set_fbbt_variant): 1 node state in LDS, 2 global scratch,
   // 0 auto = LDS while it leaves room for several waves per CU.
-  const size_t lds = quad_lds_bytes(q.dq);
-  int variant = c->fbbt_variant;
-  if (variant != 1 && variant != 2) variant = lds <= 40 * 1024 ? 1 : 2;  // 0 auto (3, 4: K1 only)
-  if (variant == 1 && lds > 160 * 1024)
-    return fail(c, MGPU_ERR_ARG, "quad LDS variant needs %zu B > 160 KiB", lds);
+  const int variant = quad_variant(q.dq, c->fbbt_variant);
+  if (variant == 0)
+    return fail(c, MGPU_ERR_ARG, "quad LDS variant needs %zu B > 160 KiB",
+                quad_lds_bytes(q.dq));
   if (variant == 2) {
     const size_t waves = ((size_t)batch + kLanes - 1) / kLanes;
     HIPCHK(c, q.scratch.ensure(waves * (2 * q.dq.nv + 2 * q.dq.maxt) * kLanes * sizeof(double)));

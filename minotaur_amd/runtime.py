@@ -39,7 +39,7 @@ EXPORTS = [
     'mgpu_bnb_round', 'mgpu_bnb_best', 'mgpu_bnb_shard', 'mgpu_bnb_config', 'mgpu_bnb_export',
     'mgpu_bnb_import', 'mgpu_strong_branch',
     'mgpu_strong_branch_dev', 'mgpu_load_qp', 'mgpu_qp_solve', 'mgpu_qp_solve_dev',
-    'mgpu_qp_plan',
+    'mgpu_qp_plan', 'mgpu_quad_plan',
     'mgpu_set_node_rows', 'mgpu_lp_solve_rows', 'mgpu_lp_solve_rows_dev', 'mgpu_bnb_brancher',
     'mgpu_bnb_relaxation',
     'mgpu_lp_refactor', 'mgpu_set_lp_pfi_wide', 'mgpu_lp_pfi_cap', 'mgpu_lp_solve_path',
@@ -192,6 +192,7 @@ def load_library():
     lib.mgpu_qp_solve.argtypes = [_P, _I, _P, _P, _I, _P, _P, _P, _P]
     lib.mgpu_qp_solve_dev.argtypes = [_P, _I, _P, _P, _I, _P, _P, _P, _P]
     lib.mgpu_qp_plan.argtypes = [_P, ctypes.POINTER(_I)]
+    lib.mgpu_quad_plan.argtypes = [_P, ctypes.POINTER(_I), ctypes.POINTER(ctypes.c_longlong)]
     lib.mgpu_set_node_rows.argtypes = [_P, _I, _I, _P, _P, _I, _P, _P, _P]
     lib.mgpu_lp_refactor.argtypes = [_P] + [_P] * 7
     lib.mgpu_lp_solve_rows.argtypes = [_P, _I] + [_P] * 6 + [_I, _I] + [_P] * 5
@@ -472,6 +473,15 @@ class Context:
         self._chk(self.lib.mgpu_quad_rows(self.h, _hp(lb), _hp(ub), _hp(rows), None),
                   'mgpu_quad_rows')
         return rows
+
+    def quad_plan(self):
+        """mgpu_quad_plan: (variant, lds_bytes) of the loaded quadratic problem
+        under the current set_fbbt_variant: 1 node state in LDS, 2 in global
+        scratch, 0 refused (LDS forced past 160 KiB)."""
+        v, n = ctypes.c_int(-1), ctypes.c_longlong(0)
+        self._chk(self.lib.mgpu_quad_plan(self.h, ctypes.byref(v), ctypes.byref(n)),
+                  'mgpu_quad_plan')
+        return v.value, n.value
 
     def quad_fbbt(self, lb, ub, rows=None, incumbent=math.inf, qt=1, mod_cap=0):
         """QuadHandler::presolveNode over host boxes [B,nv] (synchronous).

@@ -5,6 +5,13 @@ Runs Minotaur's own QuadHandler::presolveNode (src/base/QuadHandler.cpp:
 oracle/ref/ref_quad.cpp into oracle/_ref/libref_fbbt.so) on seeded QCQPs and
 node boxes, and stores inputs + outputs as small .npz fixtures:
 
+  quad_edge_<case>.npz : the same for the named cases of tests/quad_cases.py
+                    that the reference can express (every micro case that starts
+                    from the root row state, the
+                    81-variable seeded shape, slow_converge), with the
+                    case's own row state and mod-log capacity; nmods may
+                    exceed the capacity there (the log keeps the first
+                    entries).
   quad_<case>.npz : the QuadProblem fields; lb_in, ub_in [B,nv]; rows_in [R]
                     (the reference's relax_ rows at the root); qt; incumbent
                     (nan = none); lb_out, ub_out [B,nv]; rows_out [B,R];
@@ -23,6 +30,7 @@ import numpy as np
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), '..', '..'))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, 'oracle'))
+sys.path.insert(0, os.path.join(ROOT, 'tests'))
 import oracle  # noqa: E402
 from minotaur_amd.quad import (_ARRAYS, from_functions, objective_at,  # noqa: E402
                                random_qcqp, random_quad_boxes)
@@ -32,10 +40,10 @@ OUT = os.path.dirname(os.path.abspath(__file__))
 CAP = 128
 
 
-def dump(name, qp, LB, UB, incumbent, qt):
-    rows = oracle.ref_quad_root_rows(qp)
-    r = oracle.ref_quad_fbbt(qp, LB, UB, incumbent, qt, rows, CAP)
-    assert int(r.nmods.max(initial=0)) <= CAP, name
+def dump(name, qp, LB, UB, incumbent, qt, rows=None, cap=CAP, overflow=False):
+    rows = oracle.ref_quad_root_rows(qp) if rows is None else rows
+    r = oracle.ref_quad_fbbt(qp, LB, UB, incumbent, qt, rows, cap)
+    assert overflow or int(r.nmods.max(initial=0)) <= cap, name
     np.savez_compressed(
         os.path.join(OUT, f'quad_{name}.npz'),
         **{k: getattr(qp, k) for k in _ARRAYS}, nv0=qp.nv0, has_obj=int(qp.has_obj),
@@ -70,7 +78,26 @@ def micro():
     return from_functions('micro', vtype, vlb, vub, funcs, clb, cub, obj=obj, obj_const=0.5)
 
 
+EDGE_SEEDED_B = 40     # boxes of the 81-variable shape kept in its fixture
+
+
+def edge():
+    """The named cases of tests/quad_cases.py.  seeded142 and seeded266 stay
+    out (fixture size; the LDS variant refuses the latter), as do wide and
+    slow_cap, which the reference cannot express."""
+    import quad_cases as qc
+    # the fixture tests start from the root row state: not mccormick_corners
+    todo = {k: v for k, v in qc.micro_cases().items() if not k.startswith('mccormick')}
+    todo['slow_converge'] = qc.slow(qc.SLOW_CONVERGE_C, qc.SLOW_LANES[0])
+    qp, LB, UB, rows, inc, qt, cap = qc.seeded('seeded81')
+    todo['seeded81'] = (qp, LB[:EDGE_SEEDED_B], UB[:EDGE_SEEDED_B], rows, inc, qt, cap)
+    for name, (qp, LB, UB, rows, inc, qt, cap) in todo.items():
+        assert LB.shape[0] <= 128 and rows.ndim == 1
+        dump(f'edge_{name}', qp, LB, UB, inc, qt, rows=rows, cap=cap, overflow=True)
+
+
 def main():
+    edge()
     qp = micro()
     LB, UB = random_quad_boxes(qp, 96, 11, edge=True)
     LB[0], UB[0] = qp.vlb, qp.vub                      # root box

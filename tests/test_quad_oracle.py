@@ -20,10 +20,16 @@ def test_quad_oracle_matches_reference_golden(name):
 
 def test_quad_fixture_coverage():
     """The fixtures exercise every outcome: infeasible and feasible nodes,
-    all mod kinds (lower, upper, both, row rewrite), both tightenQuad_ modes."""
-    kinds, infeas, qts = set(), set(), set()
+    all mod kinds (lower, upper, both, row rewrite), both tightenQuad_ modes;
+    implied-integer variables, an infinite bound in an input box, and a node
+    with more mods than its log holds."""
+    kinds, infeas, qts, vtypes = set(), set(), set(), set()
+    inf_in = overflow = False
     for name in cases('quad_'):
-        _, g = load_quad(name)
+        qp, g = load_quad(name)
+        vtypes |= set(qp.vtype.tolist())
+        inf_in |= bool(np.isinf(g['lb_in']).any() or np.isinf(g['ub_in']).any())
+        overflow |= bool((g['nmods'] > g['mod_cap']).any())
         infeas |= set(np.unique(g['infeas']).tolist())
         qts.add(g['qt'])
         for b in range(len(g['nmods'])):
@@ -31,6 +37,8 @@ def test_quad_fixture_coverage():
     assert {0, 1} <= infeas
     assert {0, 1, 2, 3} <= kinds
     assert qts == {0, 1}
+    assert {2, 3} <= vtypes          # ImplBin, ImplInt
+    assert inf_in and overflow
 
 
 def test_quad_rows_per_node_stride():
