@@ -798,15 +798,50 @@ int mgpu_glob_config(mgpu_ctx *ctx, int order, int warm, int qt, int lin, int ob
  *      pruned, or modified and re-solved), updateAfterSolve's pseudocost per
  *      node.  One node per round (the reference's sequence; the host runs the
  *      node's loop, the device every presolve, LP and decision); needs order
- *      2, warm 1 and lin 1. */
+ *      2, warm 1 and lin 1;
+ *   2  relstronger for rounds of any width (the same prerequisites, the same
+ *      error at mgpu_glob_init otherwise): the brancher runs on the device
+ *      (glob_rel.hip) and the host moves all nodes of the round through
+ *      PCBProcessor::process's loop in lockstep.  The rule for a round of
+ *      nb > 1 nodes:
+ *      - selection: the order-2 pop (the heap top, lazy pruning by the
+ *        incumbent, up to batch nodes); "node order" is this pop order;
+ *      - every node sees the round-start incumbent (the lazy prune,
+ *        maxchange = incumbent - node value, K2's cutoff, the linear
+ *        presolve's objective bound, IntVarHandler's guided dive), the
+ *        round-start best point and the round-start pseudocosts, plus the
+ *        observations it made itself earlier in its own processing -- its
+ *        updateAfterSolve observation and the updatePCost_ pairs of its own
+ *        strong-branched candidates -- applied in the order made (a node
+ *        re-solved after a modification calls findBranches again and sees
+ *        them);
+ *      - per node exactly kind 1's loop: presolve, LP, decide; updateAfter-
+ *        Solve on the first pass only; feasible -> incumbent candidate;
+ *        separation of the squares with a re-solve; findBranches with the
+ *        outcomes branch / prune / modified -> presolve -> re-solve / no
+ *        candidate; the engine's basis chained per node and saved for the
+ *        children before strong branching;
+ *      - at the end of the round, node by node in node order: the node's
+ *        observation log is folded into the shared pseudocosts with
+ *        updatePCost_'s running mean in the order made, its incumbent
+ *        candidate is taken with its point when strictly better than the
+ *        current one, its decision is counted, and its children are created
+ *        (consecutive ids) in kind 1's order with the same branching record.
+ *      With one node selected (the root round always; root OBBT lives only
+ *      there) this is kind 1's sequence.  A full observation log ends the
+ *      round with MGPU_ERR_NOMEM naming the node; a K2 failure on a child
+ *      or an unhandled LP status with MGPU_ERR_ENGINE.  Wide best-first
+ *      rounds process more nodes than the reference's sequence does. */
 int mgpu_glob_brancher(mgpu_ctx *ctx, int kind);
 int mgpu_glob_init(mgpu_ctx *ctx, int capacity, double incumbent);
 int mgpu_glob_round(mgpu_ctx *ctx, int batch, double incumbent, mgpu_glob_stats *stats);
 int mgpu_glob_best(mgpu_ctx *ctx, double *obj, double *x);
-/* relstronger trees (mgpu_glob_brancher 1): the main engine's solves since
+/* relstronger trees (mgpu_glob_brancher 1, 2): the main engine's solves since
  * mgpu_glob_init in order -- node LPs, re-solves and strong-branching LPs --
  * as (status, value incl. constant, pivots); at most cap written (any array
- * may be NULL); returns the count. */
+ * may be NULL); returns the count.  Kind 2 logs a round node-major: all of
+ * the round's first node's solves in order, then the second node's, and so
+ * on (the order kind 1 would make them in). */
 int mgpu_glob_lp_log(mgpu_ctx *ctx, int cap, int32_t *status, double *value, int32_t *iters);
 
 /* ---- QP relaxation with an MFMA KKT block (K5) ---------------

@@ -88,6 +88,85 @@ struct GlobIO {
   uint8_t *fflag;               // [nb][M] the rows' BFlag
 };
 
+// ---- relstronger in lockstep (mgpu_glob_brancher 2; glob_rel.hip) ----------
+// A node of the round, by its position in the round: where it stands in
+// PCBProcessor::process's loop and StrongBrancher::findBranches' state.
+enum RsPhase : int32_t {
+  kRsDone = 0,      // decided: dec holds the node's decision
+  kRsDecided = 1,   // glob_decide just ran on it: separation, then findBranches
+  kRsChild = 2,     // a strong-branching child (cand cur, side) is under way
+  kRsMod = 3,       // the brancher's modification: presolve, re-solve, decide
+  kRsSep = 4,       // tangent cuts were added: re-solve, decide
+};
+
+struct RsNode {
+  int32_t phase, pass;          // pass: the solves of the process loop so far
+  int32_t cur, cnt, side;       // the candidate under way (its variable), strong-branched so far
+  int32_t iend;                 // where the candidate loop stopped (variable index)
+  int32_t status, mdown;        // 0 none / 1 prune / 2 mod (and its direction)
+  int32_t sres[2];              // the candidate's (status, value): down, up
+  int32_t dec;                  // the node's decision when done
+  int32_t bc, bdir, nrel;       // best candidate, its direction (setDir; -1 unset), reliable count
+  int32_t has_basis, ch_ok;     // the engine holds a basis / the children got one
+  int32_t lps, sb_lps, resolves, pivots;
+  int32_t o_var, o_isint, o_dir;   // the branching: variable, handler, direction
+  int32_t b_var, b_isint;       // the branching that made the node (BrInfo)
+  double ores[2];
+  double best, minscore, last_val, objval, maxchange;
+  double o_v, o_dd, o_ud;       // x_var and the candidate's distances
+  double b_act, b_dd, b_ud, b_plb;
+};
+
+struct RsLog {                  // a step's main-engine solve of one node
+  int32_t flag, status, iters, pad;
+  double value;
+};
+
+struct RsObs {                  // one updatePCost_ call: node, variable * 2 + down
+  int32_t node, vd;
+  double cost;
+};
+
+// the step's read-back: counts of the nodes by what they wait for, the
+// separation pass's cuts and flagged nodes, an error (1 K2 failed on a
+// strong-branching child or a modification, 2 the observation log is full)
+struct RsHdr {
+  int32_t n_child, n_mod, n_sep, n_cold, err, err_node, nobs, pad;
+  unsigned long long cuts, flagged;
+};
+
+struct RsIO {
+  int obs_cap;
+  double inc;                   // the round-start incumbent
+  RsNode *node;                 // [nb]
+  double *nlb, *nub, *nrec;     // [nb][nv], [nb][R + T]: the node's box and record
+  int8_t *ck, *ci;              // [nb][nv] candidate: 0 none / 1 reliable / 2 unreliable; handler
+  double *cdd, *cud, *cvio;     // [nb][nv]
+  double *lpu, *lpd;            // [nb][nv] the node-local pseudocosts
+  int32_t *ltu, *ltd;           // [nb][nv] and their counts
+  const double *spu, *spd;      // [nv] the round-start pseudocosts
+  const int32_t *stu, *std_;
+  int32_t *cb_head, *ch_head;   // [nb][m] the engine's basis, the children's
+  int8_t *cb_st, *ch_st;        // [nb][N]
+  int32_t *skip;                // [4][nb] LP masks: child warm / cold, re-solve warm / cold
+  int32_t *lst, *lit;           // [4][nb] those calls' results
+  double *lobj;
+  int32_t *only, *sdec;         // [nb] glob_decide's mask; glob_separate's decisions
+  RsHdr *hdr;
+  RsLog *log;                   // [nb] (directly after hdr)
+  RsObs *obs;                   // [obs_cap]
+  const int32_t *cs;            // [nb][2] children's pool slots: down, up (-1 none)
+};
+
+hipError_t launch_rs_init(const GlobIO &io, const RsIO &rs, hipStream_t stream);
+hipError_t launch_rs_sdec(const GlobIO &io, const RsIO &rs, hipStream_t stream);
+hipError_t launch_rs_post(const GlobIO &io, const RsIO &rs, hipStream_t stream);
+hipError_t launch_rs_counts(const GlobIO &io, const RsIO &rs, hipStream_t stream);
+hipError_t launch_rs_child(const GlobIO &io, const RsIO &rs, hipStream_t stream);
+hipError_t launch_rs_masks(const GlobIO &io, const RsIO &rs, hipStream_t stream);
+hipError_t launch_rs_absorb(const GlobIO &io, const RsIO &rs, hipStream_t stream);
+hipError_t launch_rs_children(const GlobIO &io, const RsIO &rs, hipStream_t stream);
+
 hipError_t launch_glob_round_tail(const GlobIO &io, hipStream_t stream);
 hipError_t launch_glob_decide(const GlobIO &io, hipStream_t stream);
 hipError_t launch_glob_pack(const GlobIO &io, hipStream_t stream);

@@ -64,7 +64,7 @@ struct GlobState {
   // the first presolveNode call only
   int order = 0, warm = 0, qt = 1, lin = 0, obbt = 0;
   mgpu_ctx *bte = nullptr;       // root OBBT's bound-tightening engine (bte_)
-  // Glob's relstronger (mgpu_glob_brancher 1): per pool slot the branching
+  // Glob's relstronger (mgpu_glob_brancher 1, 2): per pool slot the branching
   // that made the node (updateAfterSolve), the pseudocosts, and the main
   // engine's last solution value (strongBranch_ reads it after a verdict of
   // the stronger mods)
@@ -83,6 +83,17 @@ struct GlobState {
   };
   std::vector<LpRec> lp_log;     // relstronger: every main-engine solve in order
   DevBuf rs_head, rs_st;         // relstronger: the node's basis for its children
+  // relstronger in lockstep (mgpu_glob_brancher 2): the per-node device state
+  // of glob_rel.hip in one buffer sized by the widest round (rs_carve), and
+  // the host's staging of a round
+  DevBuf rs_buf;
+  std::vector<RsNode> rs_hnode;
+  std::vector<RsObs> rs_hobs;
+  std::vector<std::vector<LpRec>> rs_nlog;   // the round's solves per node
+  std::vector<std::vector<RsObs>> rs_nobs;   // the round's observations per node
+  std::vector<char> rs_blk;
+  std::vector<double> rs_hpc;
+  std::vector<int32_t> rs_htm, rs_hcs;
   std::vector<GHeap> heap;
   std::vector<int> free_slots;
   long long next_id = 1;
@@ -115,10 +126,35 @@ struct GlobState {
                       &pws_head, &pws_st, &pws_ok, &gsel, &cslots, &glb, &gub, &grows, &gtan,
                       &gdepth, &ghead, &gst, &gok, &skip_a, &wo_head, &wo_st, &wo_d, &wo_binv,
                       &lrptr, &ltvar, &ltsrc, &ltrow, &lrhsrc, &lcptr, &lcterm, &loidx, &ltval,
-                      &lrlo, &lrhi, &loval, &flb, &fub, &finf, &fflag, &rs_head, &rs_st})
+                      &lrlo, &lrhi, &loval, &flb, &fub, &finf, &fflag, &rs_head, &rs_st, &rs_buf})
       b->release();
     if (bte) mgpu_destroy(bte);
     bte = nullptr;
+  }
+  // The next tree of the same context takes over the buffers sized by the
+  // round (ensure_glob_batch; every use is behind an ensure of its own size)
+  // and the OBBT engine, so a tree at a batch seen before allocates nothing
+  // inside a round.
+  void adopt_round_buffers(GlobState &old) {
+    DevBuf *mine[] = {&wlb, &wub, &wrows, &x, &cand, &kinf, &knm, &st, &it, &dec, &bvar, &pos,
+                      &depth_in, &obj, &bval, &bup, &bint, &out, &wvals, &flag, &skip2, &st2,
+                      &it2, &skip_a, &obj2, &x2, &acc, &gsel, &cslots, &glb, &gub, &grows, &gtan,
+                      &gdepth, &ghead, &gst, &gok, &wo_head, &wo_st, &wo_d, &wo_binv, &flb, &fub,
+                      &finf, &fflag, &rs_buf};
+    DevBuf *theirs[] = {&old.wlb, &old.wub, &old.wrows, &old.x, &old.cand, &old.kinf, &old.knm,
+                        &old.st, &old.it, &old.dec, &old.bvar, &old.pos, &old.depth_in, &old.obj,
+                        &old.bval, &old.bup, &old.bint, &old.out, &old.wvals, &old.flag,
+                        &old.skip2, &old.st2, &old.it2, &old.skip_a, &old.obj2, &old.x2, &old.acc,
+                        &old.gsel, &old.cslots, &old.glb, &old.gub, &old.grows, &old.gtan,
+                        &old.gdepth, &old.ghead, &old.gst, &old.gok, &old.wo_head, &old.wo_st,
+                        &old.wo_d, &old.wo_binv, &old.flb, &old.fub, &old.finf, &old.fflag,
+                        &old.rs_buf};
+    static_assert(sizeof mine == sizeof theirs, "the same buffers on both sides");
+    for (size_t k = 0; k < sizeof mine / sizeof mine[0]; ++k) {
+      std::swap(mine[k]->p, theirs[k]->p);
+      std::swap(mine[k]->bytes, theirs[k]->bytes);
+    }
+    std::swap(bte, old.bte);
   }
 };
 
@@ -132,8 +168,72 @@ void glob_state_free(mgpu_ctx *c) {
 
 namespace {
 
+// The lockstep brancher's device arrays (glob_internal.h RsIO) for rounds of
+// up to B nodes, carved from one buffer at `base`; *total: the bytes needed.
+// The observation log holds 128 entries per node of the widest round: a
+// findBranches call makes at most 2 maxCands_ = 40, so only a node that
+// re-solves after modifications several times over, in a round where every
+// other node does too, could fill it (the round then ends with an error).
+RsIO rs_carve(const GlobState &s, int B, int m, int N, uintptr_t base, size_t *total) {
+  size_t off = 0;
+  auto take = [&](size_t bytes) {
+    const uintptr_t p = base + off;
+    off += (bytes + 15) & ~(size_t)15;
+    return p;
+  };
+  const size_t b = (size_t)B, nv = (size_t)s.nv, RT = (size_t)(s.R + s.T > 0 ? s.R + s.T : 1);
+  RsIO r{};
+  r.obs_cap = B * 128 + 256;
+  r.node = (RsNode *)take(b * sizeof(RsNode));
+  r.nlb = (double *)take(b * nv * 8);
+  r.nub = (double *)take(b * nv * 8);
+  r.nrec = (double *)take(b * RT * 8);
+  r.ck = (int8_t *)take(b * nv);
+  r.ci = (int8_t *)take(b * nv);
+  r.cdd = (double *)take(b * nv * 8);
+  r.cud = (double *)take(b * nv * 8);
+  r.cvio = (double *)take(b * nv * 8);
+  r.lpu = (double *)take(b * nv * 8);
+  r.lpd = (double *)take(b * nv * 8);
+  r.ltu = (int32_t *)take(b * nv * 4);
+  r.ltd = (int32_t *)take(b * nv * 4);
+  r.spu = (const double *)take(2 * nv * 8);
+  r.spd = r.spu + nv;
+  r.stu = (const int32_t *)take(2 * nv * 4);
+  r.std_ = r.stu + nv;
+  r.cb_head = (int32_t *)take(b * (size_t)m * 4);
+  r.ch_head = (int32_t *)take(b * (size_t)m * 4);
+  r.cb_st = (int8_t *)take(b * (size_t)N);
+  r.ch_st = (int8_t *)take(b * (size_t)N);
+  r.skip = (int32_t *)take(4 * b * 4);
+  r.lst = (int32_t *)take(4 * b * 4);
+  r.lit = (int32_t *)take(4 * b * 4);
+  r.lobj = (double *)take(4 * b * 8);
+  r.only = (int32_t *)take(b * 4);
+  r.sdec = (int32_t *)take(b * 4);
+  static_assert(sizeof(RsHdr) % 16 == 0, "the log follows the header");
+  r.hdr = (RsHdr *)take(sizeof(RsHdr));
+  r.log = (RsLog *)take(b * sizeof(RsLog));
+  r.obs = (RsObs *)take((size_t)r.obs_cap * sizeof(RsObs));
+  *total = off;
+  return r;
+}
+
 int ensure_glob_batch(mgpu_ctx *c, GlobState &s, int B) {
   if (B <= s.maxb) return MGPU_OK;
+  if (s.brancher == 2) {
+    size_t total = 0;
+    (void)rs_carve(s, B, c->lp.m, s.nv + c->lp.m, 0, &total);
+    HIPCHK(c, s.rs_buf.ensure(total));
+    // the host's staging, so that a round of a width seen before allocates
+    // nothing on either side
+    s.rs_hnode.reserve((size_t)B);
+    s.rs_hobs.reserve((size_t)B * 128 + 256);
+    s.rs_nlog.resize((size_t)B);
+    s.rs_nobs.resize((size_t)B);
+    s.rs_blk.reserve(sizeof(RsHdr) + (size_t)B * sizeof(RsLog));
+    s.rs_hcs.reserve((size_t)B * 2);
+  }
   const size_t nv = (size_t)s.nv, R = (size_t)(s.R > 0 ? s.R : 1);
   HIPCHK(c, s.wlb.ensure((size_t)B * nv * 8));
   HIPCHK(c, s.wub.ensure((size_t)B * nv * 8));
@@ -1109,14 +1209,243 @@ int glob_node_rs(mgpu_ctx *c, GlobState &s, GlobIO &io, const GHeap &node,
   }
 }
 
+// ---- relstronger for a round of nb > 1 nodes (mgpu_glob_brancher 2) --------
+// The rule is at the top of glob_rel.hip.  The round's first presolve, LP and
+// decide ran in mgpu_glob_round; from there every node walks glob_node_rs's
+// loop, all nodes in lockstep: a step stages the strong-branching children
+// and modifications (rs_child), presolves them in one batch, solves them
+// (children: iteration limit 50; re-solves: the default) under skip masks,
+// and absorbs the results (rs_absorb); nodes re-solved after a modification
+// or a tangent cut are decided and separated again (glob_decide,
+// glob_separate, rs_post).  One small block comes back per step: the counts
+// of nodes by what they wait for and the step's solves for the LP log.  The
+// launches always cover all nb positions; what a node does in a step is a
+// phase test in the kernels and a skip mask in the LP calls.
+int glob_rs_lockstep(mgpu_ctx *c, GlobState &s, GlobIO &io, const std::vector<GHeap> &popped,
+                     mgpu_glob_stats *stats) {
+  const int nb = io.nb, nv = s.nv, T = s.T, m = c->lp.m, N = nv + m;
+  hipStream_t stream = c->stream;
+  size_t total = 0;
+  RsIO rs = rs_carve(s, s.maxb, m, N, (uintptr_t)s.rs_buf.p, &total);
+  rs.inc = s.inc;
+  // the round-start state every node sees
+  const double inc0 = s.inc;
+  const std::vector<double> bx0 = s.best_x;
+  s.rs_hnode.assign((size_t)nb, RsNode{});
+  for (int b = 0; b < nb; ++b) {
+    const GlobState::BrInfo &bi = s.pinfo[(size_t)popped[(size_t)b].slot];
+    RsNode &n = s.rs_hnode[(size_t)b];
+    n.b_var = bi.var;
+    n.b_isint = bi.isint;
+    n.b_act = bi.act;
+    n.b_dd = bi.dd;
+    n.b_ud = bi.ud;
+    n.b_plb = bi.plb;
+    s.rs_nlog[(size_t)b].clear();
+    s.rs_nobs[(size_t)b].clear();
+  }
+  s.rs_hpc.resize((size_t)nv * 2);
+  s.rs_htm.resize((size_t)nv * 2);
+  for (int j = 0; j < nv; ++j) {
+    s.rs_hpc[(size_t)j] = s.pc_up[(size_t)j];
+    s.rs_hpc[(size_t)(nv + j)] = s.pc_dn[(size_t)j];
+    s.rs_htm[(size_t)j] = (int32_t)s.tm_up[(size_t)j];
+    s.rs_htm[(size_t)(nv + j)] = (int32_t)s.tm_dn[(size_t)j];
+  }
+  HIPCHK(c, hipMemcpyAsync(rs.node, s.rs_hnode.data(), (size_t)nb * sizeof(RsNode),
+                           hipMemcpyHostToDevice, stream));
+  HIPCHK(c, hipMemcpyAsync(const_cast<double *>(rs.spu), s.rs_hpc.data(), (size_t)nv * 16,
+                           hipMemcpyHostToDevice, stream));
+  HIPCHK(c, hipMemcpyAsync(const_cast<int32_t *>(rs.stu), s.rs_htm.data(), (size_t)nv * 8,
+                           hipMemcpyHostToDevice, stream));
+  HIPCHK(c, hipMemsetAsync(rs.hdr, 0, sizeof(RsHdr), stream));
+  HIPCHK(c, launch_rs_init(io, rs, stream));
+  GlobIO sio = io;   // glob_separate: only the nodes just decided
+  sio.dec = rs.sdec;
+  GlobIO dio = io;   // glob_decide: only the nodes just re-solved
+  dio.only = rs.only;
+  GlobIO pio = io;   // the presolve of the staged children / modifications
+  pio.flb_in = io.glb;
+  pio.fub_in = io.gub;
+  pio.frows = io.grows;
+  pio.ftan = io.gtan;
+  pio.in_tan = io.gtan;
+  LpWarmOut wo{s.wo_head.as<int32_t>(), s.wo_st.as<int8_t>(), s.wo_d.as<double>(),
+               s.wo_binv.as<double>()};
+  auto lp = [&](int call, bool warm, int limit) {
+    const size_t o = (size_t)call * nb;
+    return lp_solve_rows_wo(c, nb, io.wlb, io.wub, rs.skip + o, io.wvals, warm ? rs.cb_head : nullptr,
+                            warm ? rs.cb_st : nullptr, warm ? 0 : 1, limit, rs.lst + o, rs.lobj + o,
+                            rs.lit + o, s.x2.as<double>(), nullptr, &wo);
+  };
+  const size_t blk_bytes = sizeof(RsHdr) + (size_t)nb * sizeof(RsLog);
+  s.rs_blk.resize(blk_bytes);
+  RsHdr hdr{};
+  long long cuts = 0;
+  bool post = true;
+  // a node strong-branches at most 20 candidates (two steps each) per pass and
+  // re-solves after a modification only with a tighter box; far below this
+  const long max_steps = 1L << 20;
+  for (long step = 0;; ++step) {
+    if (post) {
+      if (T > 0) {   // separate_: the squares' tangents (glob_separate)
+        HIPCHK(c, hipMemsetAsync(s.acc.p, 0, 16, stream));
+        HIPCHK(c, launch_rs_sdec(io, rs, stream));
+        HIPCHK(c, launch_glob_separate(sio, stream));
+      }
+      HIPCHK(c, launch_rs_post(io, rs, stream));
+    }
+    HIPCHK(c, launch_rs_counts(io, rs, stream));
+    HIPCHK(c, hipMemcpyAsync(s.rs_blk.data(), rs.hdr, blk_bytes, hipMemcpyDeviceToHost, stream));
+    HIPCHK(c, hipStreamSynchronize(stream));
+    std::memcpy(&hdr, s.rs_blk.data(), sizeof hdr);
+    const RsLog *lg = reinterpret_cast<const RsLog *>(s.rs_blk.data() + sizeof(RsHdr));
+    for (int b = 0; b < nb; ++b)
+      if (lg[b].flag) s.rs_nlog[(size_t)b].push_back({lg[b].status, lg[b].iters, lg[b].value});
+    if (post && T > 0) cuts += (long long)hdr.cuts;
+    if (hdr.err == 1)
+      return fail(c, MGPU_ERR_ENGINE, "mgpu_glob_round: K2 failed on a strong-branching child or "
+                  "a modification of node %d of the round", hdr.err_node);
+    if (hdr.err == 2)
+      return fail(c, MGPU_ERR_NOMEM, "mgpu_glob_round: the observation log (%d entries) is full "
+                  "at node %d of the round", rs.obs_cap, hdr.err_node);
+    if (hdr.n_child + hdr.n_mod + hdr.n_sep == 0) break;
+    if (step >= max_steps)
+      return fail(c, MGPU_ERR_ENGINE, "mgpu_glob_round: the lockstep did not end in %ld steps",
+                  max_steps);
+    HIPCHK(c, launch_rs_child(io, rs, stream));
+    if (hdr.n_child + hdr.n_mod > 0) {   // the handlers' presolveNode on the staged boxes
+      HIPCHK(c, launch_glob_linear(pio, stream));
+      int r2 = mgpu_quad_fbbt_dev(c, nb, io.flb, io.fub, s.inc, s.qt, io.grows, 0, s.wlb.as<double>(),
+                                  s.wub.as<double>(), s.wrows.as<double>(), s.kinf.as<int32_t>(),
+                                  s.knm.as<int32_t>(), 0, nullptr, nullptr, nullptr, nullptr);
+      if (r2 != MGPU_OK) return r2;
+      HIPCHK(c, launch_glob_linear_verdict(pio, stream));
+      if (T > 0) HIPCHK(c, launch_glob_pack(pio, stream));
+    }
+    HIPCHK(c, launch_rs_masks(io, rs, stream));
+    int rc = MGPU_OK;
+    if (hdr.n_child > 0) {
+      rc = lp(0, true, kSbIter);
+      if (rc == MGPU_OK && hdr.n_cold > 0) rc = lp(1, false, kSbIter);
+    }
+    if (rc == MGPU_OK && hdr.n_mod + hdr.n_sep > 0) {
+      rc = lp(2, true, 0);
+      if (rc == MGPU_OK && hdr.n_cold > 0) rc = lp(3, false, 0);
+    }
+    if (rc != MGPU_OK) return rc;
+    HIPCHK(c, launch_rs_absorb(io, rs, stream));
+    post = hdr.n_mod + hdr.n_sep > 0;
+    if (post) HIPCHK(c, launch_glob_decide(dio, stream));
+  }
+  // ---- the end of the round, node by node in node order ----
+  s.rs_hobs.resize((size_t)(hdr.nobs > 0 ? hdr.nobs : 0));
+  s.rs_blk.resize((size_t)nb * 8);   // (the nodes' LP values, for the incumbent candidates)
+  HIPCHK(c, hipMemcpyAsync(s.rs_hnode.data(), rs.node, (size_t)nb * sizeof(RsNode),
+                           hipMemcpyDeviceToHost, stream));
+  if (hdr.nobs > 0)
+    HIPCHK(c, hipMemcpyAsync(s.rs_hobs.data(), rs.obs, (size_t)hdr.nobs * sizeof(RsObs),
+                             hipMemcpyDeviceToHost, stream));
+  HIPCHK(c, hipMemcpyAsync(s.rs_blk.data(), io.obj, (size_t)nb * 8, hipMemcpyDeviceToHost, stream));
+  HIPCHK(c, hipStreamSynchronize(stream));
+  const double *objv = reinterpret_cast<const double *>(s.rs_blk.data());
+  for (const RsObs &ob : s.rs_hobs) s.rs_nobs[(size_t)ob.node].push_back(ob);   // (in the order made)
+  s.rs_hcs.assign((size_t)nb * 2, -1);
+  std::vector<GHeap> kids;
+  long long ndec4 = 0;
+  for (int b = 0; b < nb; ++b) {
+    const RsNode &n = s.rs_hnode[(size_t)b];
+    for (const RsObs &ob : s.rs_nobs[(size_t)b]) {   // updatePCost_ (:645-650)
+      const size_t j = (size_t)(ob.vd >> 1);
+      if (ob.vd & 1) {
+        s.pc_dn[j] = (s.pc_dn[j] * s.tm_dn[j] + ob.cost) / (s.tm_dn[j] + 1);
+        s.tm_dn[j] += 1;
+      } else {
+        s.pc_up[j] = (s.pc_up[j] * s.tm_up[j] + ob.cost) / (s.tm_up[j] + 1);
+        s.tm_up[j] += 1;
+      }
+    }
+    for (const GlobState::LpRec &r : s.rs_nlog[(size_t)b]) s.lp_log.push_back(r);
+    s.tot.ndec[n.dec] += 1;
+    s.tot.lps += n.lps;
+    s.tot.pivots += n.pivots;
+    s.tot.sb_lps += n.sb_lps;
+    s.tot.resolves += n.resolves;
+    if (n.dec == 4) ++ndec4;
+    if (n.dec == 3 && objv[b] < s.inc) {
+      s.inc = objv[b];
+      HIPCHK(c, hipMemcpy(s.best_x.data(), s.x.as<double>() + (size_t)b * nv, (size_t)nv * 8,
+                          hipMemcpyDeviceToHost));
+    }
+    if (n.dec != 0) continue;
+    // the children (QuadHandler::getBranches down, up; IntVarHandler's guided
+    // dive on the round-start incumbent, else the candidate's direction)
+    const int j = n.o_var;
+    const bool isint = n.o_isint != 0, up_first = n.o_dir != 0;
+    bool down_first = true;
+    if (isint) {
+      down_first = !up_first;
+      if (std::isfinite(inc0) && !std::isnan(bx0[(size_t)j])) down_first = bx0[(size_t)j] < n.o_v;
+    }
+    if (isint) s.tot.br_int += 1;
+    else s.tot.br_cont += 1;
+    for (int k = 0; k < 2; ++k) {
+      const bool upc = down_first ? k == 1 : k == 0;
+      int slot;
+      if (!s.free_slots.empty()) {
+        slot = s.free_slots.back();
+        s.free_slots.pop_back();
+      } else {
+        if (s.hw >= s.cap)
+          return fail(c, MGPU_ERR_NOMEM, "mgpu_glob_round: node pool full (%d slots)", s.cap);
+        slot = s.hw++;
+      }
+      s.rs_hcs[(size_t)(2 * b + (upc ? 1 : 0))] = slot;
+      GlobState::BrInfo bi;
+      bi.var = j;
+      bi.isint = n.o_isint;
+      bi.act = isint ? n.o_v : (upc ? 1.0 : -1.0);
+      bi.dd = n.o_dd;
+      bi.ud = n.o_ud;
+      bi.plb = n.objval;
+      s.pinfo[(size_t)slot] = bi;
+      kids.push_back(GHeap{n.objval, popped[(size_t)b].depth + 1, s.next_id++, slot});
+    }
+  }
+  if (!kids.empty()) {
+    HIPCHK(c, hipMemcpyAsync(s.cslots.p, s.rs_hcs.data(), (size_t)nb * 8, hipMemcpyHostToDevice,
+                             stream));
+    rs.cs = s.cslots.as<int32_t>();
+    HIPCHK(c, launch_rs_children(io, rs, stream));
+    HIPCHK(c, hipStreamSynchronize(stream));
+  }
+  for (const GHeap &k : kids) {
+    s.heap.push_back(k);
+    std::push_heap(s.heap.begin(), s.heap.end(), gheap_greater);
+  }
+  s.count = (int)s.heap.size();
+  s.tot.rounds += 1;
+  s.tot.nodes += nb;
+  s.tot.cuts += cuts;
+  s.tot.open = s.count;
+  s.tot.last_batch = nb;
+  s.tot.incumbent = s.inc;
+  if (stats) *stats = s.tot;
+  if (ndec4 > 0)
+    return fail(c, MGPU_ERR_ENGINE, "mgpu_glob_round: %lld nodes ended with an engine problem "
+                "(K2 propagation cap / default bound, or an unbounded / unknown LP status)", ndec4);
+  return MGPU_OK;
+}
+
 }  // namespace
 
 extern "C" {
 
 int mgpu_glob_brancher(mgpu_ctx *c, int kind) {
   if (!c) return MGPU_ERR_ARG;
-  if (kind < 0 || kind > 1)
-    return fail(c, MGPU_ERR_ARG, "mgpu_glob_brancher: kind %d (0 MaxVio, 1 relstronger)", kind);
+  if (kind < 0 || kind > 2)
+    return fail(c, MGPU_ERR_ARG, "mgpu_glob_brancher: kind %d (0 MaxVio, 1 relstronger one node "
+                "per round, 2 relstronger batched)", kind);
   c->glob_brancher = kind;
   return MGPU_OK;
 }
@@ -1151,8 +1480,9 @@ int mgpu_glob_init(mgpu_ctx *c, int capacity, double incumbent) {
   if (capacity < 1) return fail(c, MGPU_ERR_ARG, "mgpu_glob_init: capacity < 1");
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  glob_state_free(c);
   GlobState *s = new GlobState();
+  if (c->glob) s->adopt_round_buffers(*c->glob);
+  glob_state_free(c);
   c->glob = s;
   const int nv = q.nv, R = q.R, m = c->lp.m, N = nv + m;
   s->nv = nv;
@@ -1163,11 +1493,11 @@ int mgpu_glob_init(mgpu_ctx *c, int capacity, double incumbent) {
   s->lin = c->glob_lin;
   s->obbt = c->glob_obbt;
   s->brancher = c->glob_brancher;
-  if (s->brancher == 1 && (s->order != 2 || s->warm != 1 || s->lin != 1))
+  if (s->brancher >= 1 && (s->order != 2 || s->warm != 1 || s->lin != 1))
     return fail(c, MGPU_ERR_ARG, "mgpu_glob_init: relstronger needs order 2, warm 1 and lin 1 "
                 "(a brancher's modification reaches p_ only through LinearHandler's "
                 "copyBndsFromRel_)");
-  if (s->brancher == 1) {
+  if (s->brancher >= 1) {
     HIPCHK(c, s->rs_head.ensure((size_t)c->lp.m * 4 + 4));
     HIPCHK(c, s->rs_st.ensure((size_t)(nv + c->lp.m)));
     s->pinfo.assign((size_t)capacity, GlobState::BrInfo{});
@@ -1494,6 +1824,12 @@ int mgpu_glob_round(mgpu_ctx *c, int batch, double incumbent, mgpu_glob_stats *s
   }
   HIPCHK(c, launch_glob_decide(io, c->stream));
   if (s.brancher == 1) return glob_node_rs(c, s, io, popped[0], stats);
+  // batched relstronger: a round of one node (the root's always is: root OBBT
+  // and the first presolveNode call's tightenQuad_ live only there) is
+  // brancher 1's sequence; wider rounds go through the loop in lockstep
+  if (s.brancher == 2)
+    return nb == 1 ? glob_node_rs(c, s, io, popped[0], stats)
+                   : glob_rs_lockstep(c, s, io, popped, stats);
   // the flagged nodes (flag / skip2) re-solved -- from the root basis (warm
   // 0) or the node's last basis refactored for its rows (warm 1) -- merged
   // back and decided again

@@ -1080,12 +1080,16 @@ class Context:
 
     def glob_brancher(self, kind):
         """mgpu_glob_brancher: the next glob_init's brancher (0 MaxVio, 1 Glob's
-        relstronger: one node per round, order 2, warm 1, lin 1)."""
+        relstronger: one node per round, order 2, warm 1, lin 1; 2 relstronger
+        batched: up to ``batch`` nodes per round, each seeing the round-start
+        incumbent and pseudocosts plus its own observations, folded in node
+        order at the end of the round; same prerequisites; with one node in
+        the round it is kind 1's sequence)."""
         self._chk(self.lib.mgpu_glob_brancher(self.h, int(kind)), 'mgpu_glob_brancher')
 
     def glob_lp_log(self):
         """mgpu_glob_lp_log: (status, value, pivots) of every main-engine solve
-        of a relstronger tree, in order."""
+        of a relstronger tree, in order (kind 2: node-major within a round)."""
         n = self.lib.mgpu_glob_lp_log(self.h, 0, None, None, None)
         if n < 0:
             self._chk(n, 'mgpu_glob_lp_log')
