@@ -954,6 +954,20 @@ double mgpu_last_kernel_ms(mgpu_ctx *ctx, const char *which);
  * unchanged).  Not a reference interface: the bench's per-kernel roofline. */
 int mgpu_set_qp_ktime(mgpu_ctx *ctx, int on);
 
+/* Self-test of the kernels' wave64 reductions (csrc/wave.h): one block of
+ * `block_threads` threads (a multiple of 64, at most 1024) on `device`, whose
+ * wave `wave` runs every helper on in_d[64] / in_i[64] and stores, per lane,
+ * what the helper leaves in that lane.  out_d and out_i are
+ * [MGPU_WAVE_SELFTEST_ROWS][64] host arrays; row r belongs to
+ *   0 wave_sum_sym (d)   1 wave_max_dpp (d)   2 wave_min_dpp (d)
+ *   3 wave_argmax_lane (d = maximum, i = lane)   4 wave_argmax_idx (d, i)
+ *   5 wave_argmax_dpp (d, i)                     6 wave_min_i32_dpp (i)
+ * and the part a helper does not produce stays zero.  Not a reference
+ * interface: the tests pin the reductions' association with it. */
+#define MGPU_WAVE_SELFTEST_ROWS 7
+int mgpu_wave_selftest(int device, int block_threads, int wave, const double *in_d,
+                       const int32_t *in_i, double *out_d, int32_t *out_i);
+
 #ifdef __cplusplus
 }
 #endif

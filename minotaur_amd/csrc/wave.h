@@ -74,10 +74,14 @@ __device__ __forceinline__ void wave_argmax(double &v, int &idx) {
 
 // ---- DPP reductions --------------------------------------------------------
 // Cross-lane moves on the VALU (DPP) instead of ds_bpermute (LDS round trip):
-// quad_perm xor 1 / xor 2, then row_ror 4 / 8 inside each 16-lane row, then
-// the four row results are combined through v_readlane.  The result is wave
-// uniform (in SGPRs).  Exchange patterns only, so any associative,
-// commutative combine gives the same answer in every lane.
+// quad_perm xor 1 / xor 2, then row_ror 4 / 8 inside each 16-lane row, after
+// which every lane of a row holds its row's result.  The maxima and minima
+// combine the four row results through v_readlane; wave_sum_sym joins them
+// with two DPP row broadcasts and reads one lane (see there: for the maxima
+// the same join saves ten instructions in all of K3P and costs its 32-eta
+// builds two or three more spilled VGPRs, so they keep the reads).  The
+// result is wave uniform (in SGPRs).  Exchange patterns only, so any
+// associative, commutative combine gives the same answer in every lane.
 constexpr int kDppXor1 = 0xB1;   // quad_perm [1,0,3,2]
 constexpr int kDppXor2 = 0x4E;   // quad_perm [2,3,0,1]
 constexpr int kDppRor4 = 0x124;  // row_ror:4
@@ -86,7 +90,9 @@ constexpr int kDppRor8 = 0x128;  // row_ror:8
 // Every pattern used here (quad_perm, row_ror, row_half_mirror, row_mirror)
 // has an in-row source for every lane and the row and bank masks are full,
 // so the "old" operand is never kept for an enabled lane; bound_ctrl makes a
-// disabled source lane read as 0, which is what the old value 0 gave.  With
+// disabled source lane read as 0, which is what the old value 0 gave.  (The
+// row broadcasts of wave_sum_sym have no source for row 0, or rows 0 and 1:
+// what those lanes receive is never used.)  With
 // it the compiler needs no v_mov_b32 0 in front of every DPP move (two of
 // the five VALU instructions of an f64 butterfly step).
 template <int CTRL>
@@ -168,12 +174,25 @@ constexpr int kDppMirror = 0x140;      // row_mirror: lane i <-> i ^ 15 in 16 la
 // (r0 + r1) + (r2 + r3).  Each step adds a lane and its partner (the same
 // two values in both), so the association is fixed: oracle/lp_dual.c
 // eta_dot restates it.  Wave uniform result.
+//
+// The rows are joined in the vector lanes: row_bcast:15 hands lane 15 of a
+// row to every lane of the next row, so after the first add row 1 holds
+// r0 + r1 and row 3 holds r2 + r3 (the operands of one add commuted, which
+// changes no bit); row_bcast:31 hands lane 31, row 1's sum, to rows 2 and 3,
+// and row 3 then holds (r0 + r1) + (r2 + r3).  Lane 63 is read; what the
+// other rows hold after these two steps is not the sum and is not used.
+// Eight vector instructions instead of the fifteen of the v_readlane join
+// (eight reads, four v_mov back into VGPRs, three adds).
+constexpr int kDppBcast15 = 0x142;  // row_bcast:15
+constexpr int kDppBcast31 = 0x143;  // row_bcast:31
 __device__ __forceinline__ double wave_sum_sym(double v) {
   v = v + dpp_f64<kDppXor1>(v);
   v = v + dpp_f64<kDppXor2>(v);
   v = v + dpp_f64<kDppHalfMirror>(v);
   v = v + dpp_f64<kDppMirror>(v);
-  return (rld(v, 0) + rld(v, 16)) + (rld(v, 32) + rld(v, 48));
+  v = dpp_f64<kDppBcast15>(v) + v;
+  v = dpp_f64<kDppBcast31>(v) + v;
+  return rld(v, 63);
 }
 
 __device__ __forceinline__ double wave_min_dpp(double v) {

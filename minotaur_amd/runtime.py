@@ -32,7 +32,7 @@ EXPORTS = [
     'mgpu_create', 'mgpu_destroy', 'mgpu_last_error', 'mgpu_set_stream',
     'mgpu_get_stream', 'mgpu_sync', 'mgpu_load_lp', 'mgpu_fbbt', 'mgpu_fbbt_dev',
     'mgpu_set_fbbt_variant', 'mgpu_set_lp_variant', 'mgpu_set_lp_pfi', 'mgpu_last_kernel_ms',
-    'mgpu_set_qp_ktime',
+    'mgpu_set_qp_ktime', 'mgpu_wave_selftest',
     'mgpu_lp_solve', 'mgpu_lp_solve_dev',
     'mgpu_node_decide_dev', 'mgpu_load_quad', 'mgpu_quad_rows', 'mgpu_quad_fbbt',
     'mgpu_quad_fbbt_dev', 'mgpu_lp_bound', 'mgpu_lp_bound_dev', 'mgpu_bnb_init',
@@ -205,6 +205,7 @@ def load_library():
     lib.mgpu_ws_write.argtypes = [_P, _I, _P, _P, _P, _P]
     lib.mgpu_lp_solve1.argtypes = [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P]
     lib.mgpu_set_qp_ktime.argtypes = [_P, _I]
+    lib.mgpu_wave_selftest.argtypes = [_I, _I, _I, _P, _P, _P, _P]
     lib.mgpu_last_kernel_ms.argtypes = [_P, ctypes.c_char_p]
     lib.mgpu_last_kernel_ms.restype = _D
     for name in EXPORTS:
@@ -224,6 +225,25 @@ def _hp(a):
 def _dp(t):
     """Device pointer of a torch CUDA tensor (or None)."""
     return None if t is None else ctypes.c_void_p(t.data_ptr())
+
+
+WAVE_SELFTEST_ROWS = 7  # MGPU_WAVE_SELFTEST_ROWS
+
+
+def wave_selftest(x, k, block_threads=64, wave=0, device=0):
+    """mgpu_wave_selftest: run csrc/wave.h's reductions on 64 doubles and 64
+    ints in wave `wave` of one `block_threads`-thread block; returns
+    (out_d, out_i), each [WAVE_SELFTEST_ROWS, 64] (row order: include/mgpu.h)."""
+    lib = load_library()
+    x, k = _np(x, np.float64), _np(k, np.int32)
+    assert x.shape == (64,) and k.shape == (64,)
+    out_d = np.empty((WAVE_SELFTEST_ROWS, 64), np.float64)
+    out_i = np.empty((WAVE_SELFTEST_ROWS, 64), np.int32)
+    rc = lib.mgpu_wave_selftest(int(device), int(block_threads), int(wave), _hp(x), _hp(k),
+                                _hp(out_d), _hp(out_i))
+    if rc != 0:
+        raise MgpuError(f'mgpu_wave_selftest failed ({rc})')
+    return out_d, out_i
 
 
 def comm_unique_id() -> bytes:
