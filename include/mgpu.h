@@ -796,14 +796,16 @@ int mgpu_glob_config(mgpu_ctx *ctx, int order, int warm, int qt, int lin, int ob
  *      every handler's node presolve (getStrongerMods), its LP chained through
  *      the engine with 50 pivots at most, stopping at a verdict (the node
  *      pruned, or modified and re-solved), updateAfterSolve's pseudocost per
- *      node.  One node per round (the reference's sequence; the host runs the
- *      node's loop, the device every presolve, LP and decision); needs order
- *      2, warm 1 and lin 1;
+ *      node.  One node per round, the reference's sequence: kind 2 with the
+ *      round's width fixed at 1, whatever batch mgpu_glob_round is given;
+ *      needs order 2, warm 1 and lin 1;
  *   2  relstronger for rounds of any width (the same prerequisites, the same
  *      error at mgpu_glob_init otherwise): the brancher runs on the device
  *      (glob_rel.hip) and the host moves all nodes of the round through
- *      PCBProcessor::process's loop in lockstep.  The rule for a round of
- *      nb > 1 nodes:
+ *      PCBProcessor::process's loop in lockstep, every presolve, LP and
+ *      decision on the device; root OBBT (mgpu_glob_config obbt 1) runs in
+ *      the same loop, between the root's first decision and its separation.
+ *      The rule for a round of nb nodes:
  *      - selection: the order-2 pop (the heap top, lazy pruning by the
  *        incumbent, up to batch nodes); "node order" is this pop order;
  *      - every node sees the round-start incumbent (the lazy prune,
@@ -815,8 +817,10 @@ int mgpu_glob_config(mgpu_ctx *ctx, int order, int warm, int qt, int lin, int ob
  *        strong-branched candidates -- applied in the order made (a node
  *        re-solved after a modification calls findBranches again and sees
  *        them);
- *      - per node exactly kind 1's loop: presolve, LP, decide; updateAfter-
- *        Solve on the first pass only; feasible -> incumbent candidate;
+ *      - per node exactly the reference's loop: presolve, LP, decide;
+ *        updateAfterSolve on the first pass only; feasible -> incumbent
+ *        candidate; at the root OBBT, with a re-solve when the root's point
+ *        leaves the tightened relaxation (not counted in resolves);
  *        separation of the squares with a re-solve; findBranches with the
  *        outcomes branch / prune / modified -> presolve -> re-solve / no
  *        candidate; the engine's basis chained per node and saved for the
@@ -826,9 +830,10 @@ int mgpu_glob_config(mgpu_ctx *ctx, int order, int warm, int qt, int lin, int ob
  *        updatePCost_'s running mean in the order made, its incumbent
  *        candidate is taken with its point when strictly better than the
  *        current one, its decision is counted, and its children are created
- *        (consecutive ids) in kind 1's order with the same branching record.
- *      With one node selected (the root round always; root OBBT lives only
- *      there) this is kind 1's sequence.  A full observation log ends the
+ *        (consecutive ids), the guided dive's side or the candidate's
+ *        direction first, each with the node's branching record.
+ *      With one node selected (the root round always) this is the
+ *      reference's own sequence, kind 1's.  A full observation log ends the
  *      round with MGPU_ERR_NOMEM naming the node; a K2 failure on a child
  *      or an unhandled LP status with MGPU_ERR_ENGINE.  Wide best-first
  *      rounds process more nodes than the reference's sequence does. */

@@ -88,7 +88,12 @@ struct GlobIO {
   uint8_t *fflag;               // [nb][M] the rows' BFlag
 };
 
-// ---- relstronger in lockstep (mgpu_glob_brancher 2; glob_rel.hip) ----------
+// ---- relstronger in lockstep (mgpu_glob_brancher 1, 2; glob_rel.hip) -------
+// reliabilitySetup(20, 50, 5) (Glob.cpp:171-181): maxCands_, the strong-
+// branching LP's pivot limit, the reliability threshold; StrongBrancher's eps_
+constexpr int kSbCands = 20, kSbIter = 50, kSbThresh = 5;
+constexpr double kSbEps = 1e-6;
+
 // A node of the round, by its position in the round: where it stands in
 // PCBProcessor::process's loop and StrongBrancher::findBranches' state.
 enum RsPhase : int32_t {
@@ -159,6 +164,7 @@ struct RsIO {
 };
 
 hipError_t launch_rs_init(const GlobIO &io, const RsIO &rs, hipStream_t stream);
+hipError_t launch_rs_obbt(const GlobIO &io, const RsIO &rs, int resolve, hipStream_t stream);
 hipError_t launch_rs_sdec(const GlobIO &io, const RsIO &rs, hipStream_t stream);
 hipError_t launch_rs_post(const GlobIO &io, const RsIO &rs, hipStream_t stream);
 hipError_t launch_rs_counts(const GlobIO &io, const RsIO &rs, hipStream_t stream);

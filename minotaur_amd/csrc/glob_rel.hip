@@ -1,13 +1,14 @@
-// Glob's relstronger for rounds of any width (mgpu_glob_brancher 2), gfx950:
-// StrongBrancher with reliabilitySetup(20, 50, 5) (Glob.cpp:171-181;
-// StrongBrancher.cpp) on every node of a glob round at once.
+// Glob's relstronger for rounds of any width (mgpu_glob_brancher 1: always
+// one node; 2: up to batch nodes), gfx950: StrongBrancher with
+// reliabilitySetup(20, 50, 5) (Glob.cpp:171-181; StrongBrancher.cpp) on every
+// node of a glob round at once.
 //
 // The reference runs PCBProcessor::process node by node: the pseudocosts
 // change after every node solve (updateAfterSolve, StrongBrancher.cpp:589-643)
 // and after every strong-branched candidate (useStrongBranchInfo_, :652-689),
 // and a node's solution enters the pool before the next node is processed.
-// A round of nb > 1 nodes follows this rule (the glob counterpart of the one
-// at the top of bnb_rel.hip):
+// A round of nb nodes follows this rule (the glob counterpart of the one at
+// the top of bnb_rel.hip):
 //   * selection: the order-2 pop of mgpu_glob_round (heap top, lazy pruning by
 //     the incumbent, up to batch nodes); "node order" is this pop order;
 //   * every node sees the round-start incumbent (lazy prune, maxchange =
@@ -16,12 +17,17 @@
 //     plus the observations it made itself earlier in its own processing
 //     (its updateAfterSolve observation and the updatePCost_ pairs of its own
 //     strong-branched candidates), applied in the order made;
-//   * per node exactly the loop of glob_node_rs (glob_runtime.cpp);
+//   * per node exactly PCBProcessor::process's loop (:214-300): solve, prune,
+//     updateAfterSolve on the first pass, feasible, at the root tightenBounds_
+//     (root OBBT, glob_obbt_node0 of glob_runtime.cpp; rs_obbt), separate,
+//     findBranches, re-solving after OBBT, a cut or a brancher modification;
 //   * at the end of the round, node by node in node order, the host folds the
 //     node's observation log into the shared pseudocosts (updatePCost_'s
 //     running mean, in the order made), takes its incumbent candidate when
 //     strictly better, counts its decision and creates its children.
-// With one node selected this is mgpu_glob_brancher 1's sequence.
+// With one node selected this is the reference's own sequence: kind 1 is this
+// code with the round's width fixed at 1, and the root's round of kind 2 is
+// always one node wide.
 //
 // The host (glob_rs_lockstep, glob_runtime.cpp) moves all nodes of the round
 // through that loop in lockstep; a node's place in it is RsNode::phase:
@@ -40,6 +46,8 @@
 // calls, rs_absorb, then for re-solved nodes glob_decide, rs_sdec,
 // glob_separate, rs_post; rs_counts closes the step):
 //   rs_init    the round's first LP into the per-node state;
+//   rs_obbt    the root after root OBBT tightened it: re-solved without a
+//              separation pass, or its candidates rebuilt by glob_decide;
 //   rs_sdec    glob_separate's view of the decisions (only the nodes just
 //              decided);
 //   rs_post    after a decision: updateAfterSolve on the first pass, the
@@ -60,8 +68,8 @@
 //              assigned in node order.
 // One lane per node, as glob_decide: every phase is a short, order-dependent
 // sequence (running means, first-maximum scans, the k-th largest vio) over at
-// most nv candidates, and bit-equality with the host path of brancher 1 needs
-// the host's operation order, which a sequential lane restates directly;
+// most nv candidates, and bit-equality with the reference needs its
+// operation order, which a sequential lane restates directly;
 // rs_children alone copies rows and is one wave per node.  A node's data is
 // indexed by its position in the round in every array (never compacted), so
 // bases, logs and candidate tables of different nodes cannot cross.
@@ -70,9 +78,6 @@
 
 namespace mgpu {
 namespace {
-
-constexpr int kSbCands = 20, kSbThresh = 5;
-constexpr double kSbEps = 1e-6;
 
 __device__ __forceinline__ double rs_score(double up, double down) {   // getScore_ (:381-389)
   return up > down ? down * 0.8 + up * 0.2 : up * 0.8 + down * 0.2;
@@ -274,7 +279,10 @@ __device__ void rs_prepare(const GlobIO &io, const RsIO &rs, int b, RsNode &n) {
 }
 
 // Handler::getBrMod of candidate (j, isint) in one direction on the box
-// lb / ub and the row state rec, in place: rs_br_mod of glob_runtime.cpp
+// lb / ub and the row state rec, in place: IntVarHandler floor / ceil of x_j;
+// QuadHandler x_j itself plus the rows of x_j's violated terms rebuilt for
+// the branch's box (getNewSqLf_, getNewBilLf_; with x_j the bilinear's second
+// factor the arguments come swapped, as in the reference)
 // (QuadHandler.cpp:616-692, 730-763; IntVarHandler.cpp:113-130)
 __device__ void rs_br_mod(const GlobIO &io, double *rec, double *lb, double *ub, const double *x,
                           int j, int isint, bool down) {
@@ -371,6 +379,20 @@ __global__ __launch_bounds__(256) void rs_init(GlobIO io, RsIO rs) {
   }
   n.pass = 1;
   n.phase = kRsDecided;
+}
+
+// The root (position 0 of its one-node round) after root OBBT wrote a
+// tightened box and record into the round's LP inputs (PCBProcessor.cpp:
+// 256-280).  resolve: its point left the tightened relaxation, so it is
+// solved again there before any separation -- kRsSep without the counted
+// re-solve; else glob_decide rebuilds its candidates for the new box.
+__global__ void rs_obbt(GlobIO io, RsIO rs, int resolve) {
+  if (resolve) {
+    rs_take_box(io, rs, 0);
+    rs.node[0].phase = kRsSep;
+  } else {
+    rs.only[0] = 1;
+  }
 }
 
 __global__ __launch_bounds__(256) void rs_sdec(GlobIO io, RsIO rs) {
@@ -626,6 +648,10 @@ hipError_t launch_lane(K kernel, const GlobIO &io, const RsIO &rs, hipStream_t s
 
 hipError_t launch_rs_init(const GlobIO &io, const RsIO &rs, hipStream_t stream) {
   return launch_lane(rs_init, io, rs, stream);
+}
+hipError_t launch_rs_obbt(const GlobIO &io, const RsIO &rs, int resolve, hipStream_t stream) {
+  hipLaunchKernelGGL(rs_obbt, dim3(1), dim3(1), 0, stream, io, rs, resolve);
+  return hipGetLastError();
 }
 hipError_t launch_rs_sdec(const GlobIO &io, const RsIO &rs, hipStream_t stream) {
   return launch_lane(rs_sdec, io, rs, stream);

@@ -43,10 +43,11 @@ def solve(ctx, qp, batch=1024, capacity=None, max_rounds=10**9, incumbent=math.i
     (incumbent, x or None, stats, seconds).  order / warm / qt / lin / obbt:
     mgpu_glob_config (order 2, warm 1 at batch 1: the reference's own glob
     tree node for node; lin 1: LinearHandler's node presolve too; obbt 1:
-    root OBBT).  brancher 1: Glob's relstronger, one node per round whatever
-    ``batch`` is (the reference's sequence); brancher 2: relstronger batched,
-    up to ``batch`` nodes per round under the round rule of
-    mgpu_glob_brancher (include/mgpu.h).  Both need order 2, warm 1, lin 1."""
+    root OBBT).  brancher 2: Glob's relstronger on the device, up to ``batch``
+    nodes per round in lockstep under the round rule of mgpu_glob_brancher
+    (include/mgpu.h), root OBBT inside the same loop; brancher 1: the same
+    with one node per round whatever ``batch`` is (the reference's sequence).
+    Both need order 2, warm 1, lin 1."""
     if not loaded:
         setup(ctx, qp, tan_slots)
     cap = capacity or 64 * batch

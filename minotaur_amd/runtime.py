@@ -1099,12 +1099,12 @@ class Context:
                                             int(obbt)), 'mgpu_glob_config')
 
     def glob_brancher(self, kind):
-        """mgpu_glob_brancher: the next glob_init's brancher (0 MaxVio, 1 Glob's
-        relstronger: one node per round, order 2, warm 1, lin 1; 2 relstronger
-        batched: up to ``batch`` nodes per round, each seeing the round-start
-        incumbent and pseudocosts plus its own observations, folded in node
-        order at the end of the round; same prerequisites; with one node in
-        the round it is kind 1's sequence)."""
+        """mgpu_glob_brancher: the next glob_init's brancher (0 MaxVio; 2 Glob's
+        relstronger on the device, order 2, warm 1, lin 1: up to ``batch``
+        nodes per round in lockstep, each seeing the round-start incumbent and
+        pseudocosts plus its own observations, folded in node order at the
+        end of the round, root OBBT inside the same loop; 1 the same with the
+        round's width fixed at 1, the reference's sequence)."""
         self._chk(self.lib.mgpu_glob_brancher(self.h, int(kind)), 'mgpu_glob_brancher')
 
     def glob_lp_log(self):

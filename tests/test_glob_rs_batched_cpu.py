@@ -73,6 +73,25 @@ def test_batch_one_is_the_node_at_a_time_restatement(squares, case, obbt):
     assert all(p == q or (math.isnan(p) and math.isnan(q)) for p, q in zip(xa, xb))
 
 
+def test_gpu_cases_reach_every_root_obbt_outcome():
+    """The trees of tests/test_glob_rs_batched_gpu.py (its wide cases and its
+    batch-1 cases) at obbt 1 reach the three outcomes of the lockstep's root
+    OBBT hook: the box tightened and the root's point infeasible to the new
+    relaxation, tightened and still feasible, nothing changed."""
+    import test_glob_rs_batched_gpu as g
+
+    class Recording(BatchedRsContext):
+        def _root_obbt(self, lb, ub, rec, x):
+            r = super()._root_obbt(lb, ub, rec, x)
+            seen.add((bool(r[0]), bool(r[1])))
+            return r
+
+    seen = set()
+    for squares, case in g.CASES + g.ONE_CASES:
+        make(squares, case, 2, cls=Recording).glob_round(1)   # the root's round
+    assert seen == {(True, False), (True, True), (False, True)}
+
+
 @pytest.mark.parametrize('batch', [4, 16])
 @pytest.mark.parametrize('squares,case', ALL_CASES)
 def test_wide_batches_close_with_the_same_optimum(squares, case, batch):

@@ -8,7 +8,10 @@ pivots equal, values to 1e-9 max(1, max |value|), the bound of
 tests/test_glob_rs_squares_gpu.py.  Widths 2, 4 and 16 (partial last rounds)
 on bilinear trees and on trees with squares (separation and re-solves inside
 wide rounds), rounds of 64 and 128 nodes, and rounds past the 256 lanes of a
-block of the lane-per-node kernels."""
+block of the lane-per-node kernels.  Kind 2 at batch 1 and kind 1 take the same
+lockstep one node wide, the root's OBBT hook included: batch 1 over ONE_CASES,
+which with OBBT on reach its three outcomes (tests/test_glob_rs_batched_cpu.py
+holds the case lists to that)."""
 import math
 
 import numpy as np
@@ -23,6 +26,8 @@ SLOTS = 8
 BIL_CASES = [(2, 10, 6), (0, 8, 5), (4, 8, 5), (1, 8, 5), (7, 8, 5), (11, 6, 4)]
 SQ_CASES = [(3, 5, 3), (33, 6, 4), (12, 5, 3)]
 CASES = [(False, c) for c in BIL_CASES] + [(True, c) for c in SQ_CASES]
+# batch 1 (trees of 19 nodes at most)
+ONE_CASES = [(False, (4, 8, 5)), (False, (1, 8, 5)), (True, (3, 5, 3)), (True, (14, 5, 3))]
 
 
 @pytest.fixture(scope='module')
@@ -33,14 +38,14 @@ def ctx():
     c.close()
 
 
-def start(ctx, squares, case, obbt, capacity=1 << 15):
+def start(ctx, squares, case, obbt, capacity=1 << 15, brancher=2):
     from minotaur_amd import glob as mglob
     seed, nv0, ncon = case
     qp = random_qcqp(seed, nv0=nv0, ncon=ncon, squares=squares)
     slots = SLOTS if squares else 0
     mglob.setup(ctx, qp, slots)
     ctx.glob_config(2, 1, 0, 1, obbt)
-    ctx.glob_brancher(2)
+    ctx.glob_brancher(brancher)
     cpu = BatchedRsContext(qp, tan_slots=slots)
     cpu.glob_config(2, 1, 0, 1, obbt)
     cpu.glob_brancher(2)
@@ -49,8 +54,9 @@ def start(ctx, squares, case, obbt, capacity=1 << 15):
     return cpu
 
 
-def compare(ctx, cpu, batch, max_rounds=5000, close=True):
-    """Round for round; returns the widths of the rounds."""
+def compare(ctx, cpu, batch, max_rounds=5000, close=True, wide=True):
+    """Round for round; returns the widths of the rounds.  wide: some round
+    must hold two nodes or more."""
     widths = []
     for _ in range(max_rounds):
         sg, sc = ctx.glob_round(batch), cpu.glob_round(batch)
@@ -76,7 +82,7 @@ def compare(ctx, cpu, batch, max_rounds=5000, close=True):
     assert np.allclose(gv[fin], cv[fin], rtol=0,
                        atol=1e-9 * max(1.0, np.abs(cv[fin]).max(initial=0)))
     # a silent fall-back to one node per round fails here
-    assert max(widths) >= 2
+    assert not wide or max(widths) >= 2
     return widths
 
 
@@ -87,6 +93,17 @@ def test_batched_relstronger_matches_cpu_restatement(ctx, squares, case, batch, 
     cpu = start(ctx, squares, case, obbt)
     widths = compare(ctx, cpu, batch)
     assert max(widths) <= batch
+
+
+@pytest.mark.parametrize('obbt', [0, 1])
+@pytest.mark.parametrize('squares,case', ONE_CASES)
+def test_batch_one_matches_cpu_restatement(ctx, squares, case, obbt):
+    """Kind 2 with every round one node wide: the lockstep on the reference's
+    own sequence, at the root with OBBT tightening and leaving the point
+    infeasible (bilinear (1,8,5)), feasible ((4,8,5), squares (3,5,3)) or
+    changing nothing (squares (14,5,3))."""
+    cpu = start(ctx, squares, case, obbt)
+    assert max(compare(ctx, cpu, 1, wide=False)) == 1
 
 
 def test_rounds_of_64_nodes(ctx):
@@ -126,6 +143,28 @@ def test_no_allocation_in_a_round_of_a_width_seen(ctx):
         s = ctx.glob_round(batch)
         assert alloc_stats() == a0, (k, s.last_batch)
         assert s.last_batch == widths[k]
+    assert s.open == 0
+
+
+def test_brancher_one_allocates_nothing_in_a_round(ctx):
+    """Kind 1 sizes the lockstep's buffers with the round as kind 2 does: a
+    second tree allocates nothing inside mgpu_glob_round."""
+    from minotaur_amd.runtime import alloc_stats
+    start(ctx, False, (0, 8, 5), 1, brancher=1)
+    rounds = 0
+    for _ in range(5000):
+        s = ctx.glob_round(1)
+        rounds += 1
+        if s.open == 0:
+            break
+    # (the last call may pop only nodes the incumbent prunes)
+    assert s.open == 0 and s.nodes == 47 <= rounds
+    ctx.glob_init(1 << 15)
+    for k in range(rounds):
+        a0 = alloc_stats()
+        s = ctx.glob_round(1)
+        assert alloc_stats() == a0, k
+        assert s.last_batch == 1
     assert s.open == 0
 
 

@@ -1,8 +1,8 @@
 """Time Glob's relstronger on bilinear QCQPs to closure: kind 1 (one node per
-round) at batch 1 against kind 2 (batched, lockstep) at batches 16, 128 and
-512, on the same library.  Per setting: a warm-up solve, then REPS timed
-solves; prints the median time to proof with the tree's nodes, rounds, LPs
-and strong-branching LPs.
+round) at batch 1 against kind 2 (batched) at batches 1, 16, 128 and 512, on
+the same library.  Per setting: a warm-up solve, then REPS timed solves;
+prints the median, minimum and maximum time to proof with the tree's nodes,
+rounds, LPs and strong-branching LPs.
 
     python tools/glob_rs_time.py [REPS [seed,nv0,ncon ...]]
 """
@@ -20,7 +20,7 @@ from minotaur_amd.quad import random_qcqp  # noqa: E402
 from minotaur_amd.runtime import Context  # noqa: E402
 
 CASES = [(0, 14, 9), (3, 14, 9), (1, 14, 9)]
-SETTINGS = [(1, 1), (2, 16), (2, 128), (2, 512)]   # (brancher, batch)
+SETTINGS = [(1, 1), (2, 1), (2, 16), (2, 128), (2, 512)]   # (brancher, batch)
 CAPACITY = 1 << 17
 
 
@@ -28,8 +28,9 @@ def main():
     reps = int(sys.argv[1]) if len(sys.argv) > 1 else 5
     cases = [tuple(int(v) for v in a.split(',')) for a in sys.argv[2:]] or CASES
     ctx = Context(0)
-    print('| case | brancher | batch | median ms | nodes | rounds | LPs | SB LPs | nodes/s |')
-    print('|---|---|---|---|---|---|---|---|---|')
+    print('| case | brancher | batch | median ms | min ms | max ms | nodes | rounds | LPs | SB LPs '
+          '| nodes/s |')
+    print('|---|---|---|---|---|---|---|---|---|---|---|')
     for seed, nv0, ncon in cases:
         qp = random_qcqp(seed, nv0=nv0, ncon=ncon, squares=False)
         mglob.setup(ctx, qp, 0)
@@ -47,8 +48,9 @@ def main():
                 ts.append(time.perf_counter() - t0)
             ts.sort()
             med = ts[len(ts) // 2]
-            print(f'| ({seed},{nv0},{ncon}) | {brancher} | {batch} | {1e3 * med:.1f} | {st.nodes} | '
-                  f'{st.rounds} | {st.lps} | {st.sb_lps} | {st.nodes / med:.0f} |', flush=True)
+            print(f'| ({seed},{nv0},{ncon}) | {brancher} | {batch} | {1e3 * med:.1f} | '
+                  f'{1e3 * ts[0]:.1f} | {1e3 * ts[-1]:.1f} | {st.nodes} | {st.rounds} | {st.lps} | '
+                  f'{st.sb_lps} | {st.nodes / med:.0f} |', flush=True)
     ctx.close()
 
 
