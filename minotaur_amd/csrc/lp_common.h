@@ -31,6 +31,17 @@ __device__ __forceinline__ double art_hi(double tlo, double ab) {
   return (tlo > -kInfB ? tlo : 0.0) + ab;
 }
 
+// A nonbasic column (status st) that sits on an artificial bound (art: bit 0
+// the lower, bit 1 the upper) when no row is infeasible (oracle box_state):
+// kBoxGrow while its reduced cost is nonzero -- the box holds it and has to
+// grow; kBoxRelease at dj = 0 -- it needs no box and goes back to its true
+// bounds.  0: neither.
+constexpr int kBoxGrow = 1, kBoxRelease = 2;
+__device__ __forceinline__ int box_state(int st, int art, double dj) {
+  if (!((st == ST_LB && (art & 1)) || (st == ST_UB && (art & 2)))) return 0;
+  return fabs(dj) > kDTol ? kBoxGrow : kBoxRelease;
+}
+
 // The problem one solve sees: the node's box, the row bounds, the objective
 // (ocol >= 0: osign * x[ocol], a bound LP; else c).
 struct LpView {
@@ -247,6 +258,18 @@ __device__ __forceinline__ void place_columns(const CS &s, bool warm, double ab,
       }
     }
     if (!keep) place_nonbasic(s, j, ab);
+  }
+}
+
+// oracle release_art
+template <class CS>
+__device__ __forceinline__ void release_art(const CS &s, int t0, int stride) {
+  for (int j = t0; j < s.N; j += stride) {
+    if (box_state(s.st[j], s.art[j], s.d[j]) != kBoxRelease) continue;
+    s.blo[j] = s.tlo(j);
+    s.bhi[j] = s.thi(j);
+    s.art[j] = 0;
+    place_nonbasic(s, j, 0.0);
   }
 }
 

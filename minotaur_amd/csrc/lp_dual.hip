@@ -465,22 +465,22 @@ __global__ __launch_bounds__(64 * W) void lp_dual_kernel(DevLP lp, LpIO io) {
           fresh = true;
           continue;
         }
-        bool grow = false;
-        for (int j = lane; j < N; j += 64) {
-          const int8_t a = C.art[j], s = C.st[j];
-          if (s == ST_BASIC || !a) continue;
-          if ((s == ST_LB && (a & 1)) || (s == ST_UB && (a & 2))) grow = true;
-        }
-        if (!__any(grow)) {
+        int box = 0;
+        for (int j = lane; j < N; j += 64) box |= box_state(C.st[j], C.art[j], C.d[j]);
+        const bool grow = __any(box & kBoxGrow);
+        if (!grow && !__any(box & kBoxRelease)) {
           status = 0;
           break;
         }
-        if (art_bound >= 1e13) {
+        if (grow && art_bound >= 1e13) {
           status = 4;
           break;
         }
-        art_bound *= 1e3;
-        grow_art(C, art_bound, lane, 64);
+        release_art(C, lane, 64);
+        if (grow) {
+          art_bound *= 1e3;
+          grow_art(C, art_bound, lane, 64);
+        }
         zB = compute_primals(C, binv);
         fresh = true;
         continue;

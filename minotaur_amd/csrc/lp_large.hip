@@ -437,22 +437,22 @@ __global__ __launch_bounds__(kT) void lp_large_kernel(DevLP lp, LpIO io, double 
           fresh = true;
           continue;
         }
-        bool grow = false;
-        for (int j = tid; j < N; j += kT) {
-          const int8_t a = s.art[j], v = s.st[j];
-          if (v == ST_BASIC || !a) continue;
-          if ((v == ST_LB && (a & 1)) || (v == ST_UB && (a & 2))) grow = true;
-        }
-        if (!blk_any(grow, s)) {
+        int box = 0;
+        for (int j = tid; j < N; j += kT) box |= box_state(s.st[j], s.art[j], s.d[j]);
+        const bool grow = blk_any(box & kBoxGrow, s);
+        if (!grow && !blk_any(box & kBoxRelease, s)) {
           status = 0;
           break;
         }
-        if (art_bound >= 1e13) {
+        if (grow && art_bound >= 1e13) {
           status = 4;
           break;
         }
-        art_bound *= 1e3;
-        grow_art(s, art_bound, tid, kT);
+        release_art(s, tid, kT);
+        if (grow) {
+          art_bound *= 1e3;
+          grow_art(s, art_bound, tid, kT);
+        }
         compute_primals(s);
         fresh = true;
         continue;

@@ -681,16 +681,20 @@ __global__ __launch_bounds__((64 * waves_for<S, K>())) void lp_pfi_kernel(PfiArg
         // optimal on the maintained primal values: the product form holds at
         // most kmax etas since the recompute at the solve's start, so no
         // second recompute confirms them (oracle: pfi mode)
-        if (!pfi_needs_growth(sa)) {
+        const int box = pfi_box_state(sa, d);
+        if (!box) {
           status = 0;
           break;
         }
-        if (art_bound >= 1e13) {
+        if ((box & kBoxGrow) && art_bound >= 1e13) {
           status = 4;
           break;
         }
-        art_bound *= 1e3;
-        pfi_grow(P, sa, zc, lo, hi, lane, art_bound);
+        pfi_release(sa, d, zc, lo, hi, lane);
+        if (box & kBoxGrow) {
+          art_bound *= 1e3;
+          pfi_grow(P, sa, zc, lo, hi, lane, art_bound);
+        }
         need = true;
         continue;
       }

@@ -168,19 +168,34 @@ __device__ __forceinline__ void pfi_grow(const PfiProb &P, int (&sa)[S], double 
   }
 }
 
-// some nonbasic column sits on an artificial bound: the box has to grow
-// before the basis counts as optimal
+// What the nonbasic columns on an artificial bound ask for before the basis
+// counts as optimal (box_state over every column): kBoxGrow | kBoxRelease
+static_assert(kArtLo == 1 << 2 && kArtHi == 2 << 2, "box_state reads the flags as bits 0 and 1");
 template <int S>
-__device__ __forceinline__ bool pfi_needs_growth(const int (&sa)[S]) {
-  bool g = false;
+__device__ __forceinline__ int pfi_box_state(const int (&sa)[S], const double (&d)[S]) {
+  int box = 0;
+#pragma unroll
+  for (int s = 0; s < S; ++s) box |= box_state(sa[s] & 3, (sa[s] >> 2) & 3, d[s]);
+  return (__any(box & kBoxGrow) ? kBoxGrow : 0) | (__any(box & kBoxRelease) ? kBoxRelease : 0);
+}
+
+// oracle release_art
+template <int S>
+__device__ __forceinline__ void pfi_release(int (&sa)[S], const double (&d)[S], double *zc,
+                                            double *lo, double *hi, int lane) {
 #pragma unroll
   for (int s = 0; s < S; ++s) {
-    const int st = sa[s] & 3;
-    if (st != ST_BASIC && (((st == ST_LB) && (sa[s] & kArtLo)) ||
-                           ((st == ST_UB) && (sa[s] & kArtHi))))
-      g = true;
+    const int j = s * 64 + lane;
+    if (box_state(sa[s] & 3, (sa[s] >> 2) & 3, d[s]) != kBoxRelease) continue;
+    // the artificial side's true bound is infinite; the other side kept its
+    // own, where place_nonbasic puts a zero reduced cost when it is finite
+    const bool at_lo = (sa[s] & 3) == ST_LB;
+    (at_lo ? lo : hi)[j] = at_lo ? -INFINITY : INFINITY;
+    const double o = (at_lo ? hi : lo)[j];
+    const bool o_f = fabs(o) < kInfB;
+    sa[s] = o_f ? (at_lo ? ST_UB : ST_LB) : ST_FREE;
+    zc[j] = o_f ? o : 0.0;
   }
-  return __any(g);
 }
 
 // some nonbasic column has an artificial bound (dual unbounded: grow or stop)

@@ -264,16 +264,20 @@ __global__ __launch_bounds__(64 * kWaves) void lp_pfiw_kernel(DevLP lp, LpIO io,
       asm volatile("" : "+v"(best));
       if (best == 0.0) {
         // optimal on the maintained primal values (K3P's rule, oracle pfi mode)
-        if (!pfi_needs_growth(sa)) {
+        const int box = pfi_box_state(sa, d);
+        if (!box) {
           status = 0;
           break;
         }
-        if (art_bound >= 1e13) {
+        if ((box & kBoxGrow) && art_bound >= 1e13) {
           status = 4;
           break;
         }
-        art_bound *= 1e3;
-        pfi_grow(P, sa, zc, lo, hi, lane, art_bound);
+        pfi_release(sa, d, zc, lo, hi, lane);
+        if (box & kBoxGrow) {
+          art_bound *= 1e3;
+          pfi_grow(P, sa, zc, lo, hi, lane, art_bound);
+        }
         primals();
         continue;
       }

@@ -210,6 +210,32 @@ static void place_nonbasic(lpw *W, int j, double art_bound) {
   }
 }
 
+/* A nonbasic column that sits on an artificial bound when no row is
+ * infeasible: BOX_GROW while its reduced cost is nonzero -- the box is what
+ * holds it, so the box has to grow (and the LP is unbounded when it cannot
+ * grow any more); BOX_RELEASE at d_j = 0 -- the column was boxed for the
+ * reduced cost it started with and pivots brought that back to zero, so it is
+ * dual feasible at any value and needs no box.  0: neither. */
+enum { BOX_GROW = 1, BOX_RELEASE = 2 };
+static int box_state(const lpw *W, int j) {
+  if (!((W->st[j] == ST_LB && (W->art[j] & 1)) || (W->st[j] == ST_UB && (W->art[j] & 2))))
+    return 0;
+  return fabs(W->d[j]) > D_TOL ? BOX_GROW : BOX_RELEASE;
+}
+
+/* Every BOX_RELEASE column back to its true bounds, placed as a column with
+ * zero reduced cost is (place_nonbasic: a finite bound, else free at 0). */
+static void release_art(lpw *W) {
+  for (int j = 0; j < W->N; ++j) {
+    if (box_state(W, j) != BOX_RELEASE) continue;
+    double tl = bnd_lo(W->P, W->lb, j), th = bnd_hi(W->P, W->ub, j);
+    W->blo[j] = tl < -INF_B ? -INFINITY : tl;
+    W->bhi[j] = th > INF_B ? INFINITY : th;
+    W->art[j] = 0;
+    place_nonbasic(W, j, 0.0);
+  }
+}
+
 /* Widen every artificial bound to the new half-width (nonbasic columns keep
  * their status and move with their bound). */
 static void grow_art(lpw *W, double art_bound) {
@@ -568,15 +594,15 @@ static int dual_simplex_impl(const orc_lp *P, const double *lb, const double *ub
     }
     if (r < 0) {
       /* optimal for the (possibly artificially boxed) LP */
-      int grow = 0;
-      for (int j = 0; j < N; ++j) {
-        if (W.st[j] == ST_BASIC || !W.art[j]) continue;
-        if ((W.st[j] == ST_LB && (W.art[j] & 1)) || (W.st[j] == ST_UB && (W.art[j] & 2))) grow = 1;
+      int box = 0;
+      for (int j = 0; j < N; ++j) box |= box_state(&W, j);
+      if (!box) { status = 0; break; }
+      if ((box & BOX_GROW) && art_bound >= 1e13) { status = 4; break; }   /* ProvenUnbounded */
+      release_art(&W);
+      if (box & BOX_GROW) {
+        art_bound *= 1e3;
+        grow_art(&W, art_bound);
       }
-      if (!grow) { status = 0; break; }
-      if (art_bound >= 1e13) { status = 4; break; }   /* ProvenUnbounded */
-      art_bound *= 1e3;
-      grow_art(&W, art_bound);
       compute_primals(&W);
       fresh = 1;
       continue;

@@ -288,6 +288,11 @@ def test_warm_basis_without_reduced_costs(ctx, name, variant):
     st, obj, it, _ = oracle.dual_simplex(q, lb, ub, ows)
     assert np.array_equal(r.status, st) and np.array_equal(r.iters, it)
     assert np.array_equal(r.obj, obj)
+    for b in range(0, lb.shape[0], 7):    # HiGHS decides the status, not the oracle
+        hs, ho = oracle.highs(q, lb[b], ub[b])
+        assert hs in (0, 2, 4) and r.status[b] == hs
+        if hs == 0:
+            assert abs(ho - r.obj[b]) <= 1e-6 * max(1.0, abs(ho))
 
 
 @pytest.mark.parametrize('variant', [0, 2])

@@ -111,6 +111,13 @@ def test_k3l_bound_lps_bitwise(ctx):
     assert np.array_equal(r.status, st)
     assert np.array_equal(r.iters, it)
     assert np.array_equal(r.obj, obj)
+    for k in range(cols.size):            # HiGHS decides the status, not the oracle
+        c = np.zeros(p.n)
+        c[cols[k]] = signs[k]
+        hs, ho = oracle.highs_obj(p, c)
+        assert hs in (0, 2, 4) and r.status[k] == hs
+        if hs == 0:
+            assert abs(ho - r.obj[k]) <= 1e-6 * max(1.0, abs(ho))
 
 
 @pytest.mark.parametrize('f,N,nodes', [(64, 256, 256), (256, 1024, 48)])

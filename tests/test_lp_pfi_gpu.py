@@ -204,11 +204,14 @@ def test_k3p_bound_lps_vs_oracle(ctx):
     st, ob, it, xs = oracle.lp_bound(p, cols, signs, ws=ows, pfi=KCAP)
     assert np.array_equal(g.status, st) and np.array_equal(g.iters, it)
     assert _close(g.obj, ob)
-    for k in np.nonzero(st == 0)[0][::17]:
+    assert (st == 0).any()
+    for k in range(0, cols.size, 17):     # whatever the status: HiGHS decides it
         c = np.zeros(p.n)
         c[cols[k]] = signs[k]
         hs, ho = oracle.highs_obj(p, c)
-        assert hs == 0 and abs(ho - g.obj[k]) <= 1e-6 * max(1.0, abs(ho))
+        assert hs in (0, 2, 4) and g.status[k] == hs
+        if hs == 0:
+            assert abs(ho - g.obj[k]) <= 1e-6 * max(1.0, abs(ho))
 
 
 def test_k3p_refuses_what_it_cannot_run(ctx):

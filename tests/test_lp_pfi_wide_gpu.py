@@ -145,11 +145,16 @@ def test_k3pw_bound_lps_vs_oracle(ctx, kmax):
     assert np.array_equal(g.status, st) and np.array_equal(g.iters, it)
     ok = st == 0
     assert np.allclose(g.obj[ok], ob[ok], rtol=1e-9, atol=1e-9)
-    for k in np.nonzero(ok)[0][::13]:
+    assert ok.any()
+    # every LP, whatever its status: 23 of these 96 once came back as a false
+    # "unbounded" from kernels and oracle alike
+    for k in range(cols.size):
         c = np.zeros(p.n)
         c[cols[k]] = signs[k]
         hs, ho = oracle.highs_obj(p, c)
-        assert hs == 0 and abs(ho - g.obj[k]) <= 1e-6 * max(1.0, abs(ho))
+        assert hs in (0, 2, 4) and g.status[k] == hs
+        if hs == 0:
+            assert abs(ho - g.obj[k]) <= 1e-6 * max(1.0, abs(ho))
 
 
 def test_k3pw_tree_matches_cpu_and_highs(ctx):
