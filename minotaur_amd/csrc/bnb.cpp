@@ -23,42 +23,12 @@
 
 #include "bnb_internal.h"
 #include "ctx.h"
+#include "node_heap.h"
 
-// Reference node order (mgpu_bnb_config order 2): TreeManager's "bfs"
-// NodeHeap with the reference's comparator valueGreaterThan (NodeHeap.cpp:
-// 24-47: bound within 1e-6, tie-break score (0 in BranchAndBound), shallower
-// first, then the larger node id), kept on the host with the same
-// std::push_heap / std::pop_heap, node ids assigned as TreeManager does
-// (root 0, children in branch order, TreeManager.cpp:97-136, 232-249), open
-// nodes pruned lazily at the top (TreeManager::getCandidate, :162-186).
-struct HeapNode {
-  double lb;
-  int depth;
-  long long id;
-  int slot;
-};
-static bool heap_greater(const HeapNode &a, const HeapNode &b) {
-  if (a.lb > b.lb + 1e-6) return true;
-  if (a.lb < b.lb - 1e-6) return false;
-  if (a.depth < b.depth) return false;
-  if (a.depth > b.depth) return true;
-  return a.id < b.id;
-}
-
-struct BnbState {
-  int n = 0, cap = 0, count = 0, maxb = 0;
-  int grow = 0;                // mgpu_bnb_growth of this tree
-  bool root_ok = false;
-  double inc = INFINITY;
-  std::vector<double> best_x;
-  mgpu_bnb_stats tot{};
-  int order = 0, warm = 0;     // mgpu_bnb_config at init
-  int qp = 0;                  // mgpu_bnb_relaxation at init: node QPs by K5
-  int rel = 0;                 // mgpu_bnb_brancher at init: 1 = reliability branching
-  long long calls = 0;         // ReliabilityBrancher stats_->calls (findBranches calls)
-  int maxsb = 0;               // strong-branching LP capacity of the child buffers
-  int hw = 0;                  // best-first: pool high-water mark
-  size_t sort_bytes = 0;
+// The tree's device buffers, all grow-only and nothing else: a new tree on the
+// same context takes the whole struct over (mgpu_bnb_init), so it reuses the
+// pool instead of freeing and allocating gigabytes again.
+struct BnbBufs {
   DevBuf plb, pub, pnlb, pdepth;
   DevBuf wlb, wub, inf, nm, st, obj, it, x, dec, cand, bvar, bval, bup, depth_in, pos, bsum,
       bidx, boff, bmin, bcnt, out;
@@ -78,61 +48,43 @@ struct BnbState {
   DevBuf ch_head, ch_st, ch_d, ch_binv, sbstop, sblist, sbcnt;
   // path warm starts (warm 2): per pool slot, per batch (gathered in) and out
   DevBuf ppk, ppath, ppst, bpk, bppath, bpst, opk, oppath, opst;
-  int inherit = 0;             // longest path handed to children (<= the eta cap)
-  // order 2: the host heap, free pool slots, next node id
-  std::vector<HeapNode> heap;
-  std::vector<HeapNode> front;  // nodes modified by the brancher: solved again next
-  std::vector<int> free_slots;
-  long long next_id = 0;
-  bool guided = true;          // IntVarHandler guided_dive (Environment.cpp:160-163)
-  DevBuf cslots;               // [2 nb] child slots
+  DevBuf cslots;               // order 2: [2 nb] child slots
   // grow-only workspaces of the migration path (shard, export, import), so a
   // rebalance inside a timed multi-GPU run allocates nothing once warm
   DevBuf mw_slots, mw_ft, mw_tmp, mw_tlb, mw_tub, mw_tnlb, mw_tdep;
-  std::vector<int> pick;       // mgpu_bnb_pick: pool slots of the picked nodes, in pick order
   // clean-row masks (mgpu_bnb_fbbt_carry; depth-first, m <= 64): per pool
   // slot the node's K1 start mask and its parent's branching variable (-1:
   // none, all rows), per batch the masks K1 carries out, and the grouping
   // pass's sort buffers (keys, node indices, the order K1 works through)
-  int carry = 0;               // the mode at init, 0 when the tree cannot use masks
-  size_t osort_bytes = 0;
   DevBuf pmask, pkey, bcarry, okeys, okeys2, ovals, ord, osort_tmp;
-  std::vector<DevBuf *> bufs() {
-    return {&plb, &pub, &pnlb, &pdepth, &wlb, &wub, &inf, &nm, &st, &obj, &it, &x,
-                      &dec, &cand, &bvar, &bval, &bup, &depth_in, &pos, &bsum, &bidx, &boff,
-                      &bmin, &bcnt, &out, &ws_head, &ws_st, &ws_d, &ws_binv, &r_st, &r_obj,
-                      &r_it, &plive, &keys, &keys2, &vals, &vals2, &sort_tmp, &counts,
-                      &pws_head, &pws_st, &pws_d, &pws_binv, &bws_head, &bws_st, &bws_d,
-                      &bws_binv, &wo_head, &wo_st, &wo_d, &wo_binv, &pc_up, &pc_dn, &cnt_up,
-                      &cnt_dn, &last, &last_new, &ppvar, &ppval, &bnlb, &bpvar, &bpval, &rflag, &rrank,
-                      &nsb, &sb_off, &sb_var, &sb_val, &dec2, &nev, &ev_var, &ev_side, &ev_cost,
-                      &rcnt, &clb, &cub, &cnode, &cst, &cobj, &cit, &ev_off, &cv_var, &cv_side,
-                      &cv_cost, &ppk, &ppath, &ppst, &bpk, &bppath, &bpst, &opk, &oppath, &opst,
-                      &cslots, &ch_head, &ch_st, &ch_d, &ch_binv, &sbstop, &sblist, &sbcnt,
-                      &mw_slots, &mw_ft, &mw_tmp, &mw_tlb, &mw_tub, &mw_tnlb, &mw_tdep,
-                      &pmask, &pkey, &bcarry, &okeys, &okeys2, &ovals, &ord, &osort_tmp};
-  }
-  void release() {
-    for (DevBuf *b : bufs()) b->release();
-  }
-  // takes over another state's device buffers (grow-only DevBufs): a new
-  // tree on the same context reuses the pool instead of freeing and
-  // allocating gigabytes again (mgpu_bnb_init)
-  void adopt(BnbState &o) {
-    std::vector<DevBuf *> a = bufs(), b = o.bufs();
-    for (size_t i = 0; i < a.size(); ++i) {
-      std::swap(a[i]->p, b[i]->p);
-      std::swap(a[i]->bytes, b[i]->bytes);
-    }
-  }
+};
+
+struct BnbState : BnbBufs {
+  int n = 0, cap = 0, count = 0, maxb = 0;
+  int grow = 0;                // mgpu_bnb_growth of this tree
+  bool root_ok = false;
+  double inc = INFINITY;
+  std::vector<double> best_x;
+  mgpu_bnb_stats tot{};
+  int order = 0, warm = 0;     // mgpu_bnb_config at init
+  int qp = 0;                  // mgpu_bnb_relaxation at init: node QPs by K5
+  int rel = 0;                 // mgpu_bnb_brancher at init: 1 = reliability branching
+  long long calls = 0;         // ReliabilityBrancher stats_->calls (findBranches calls)
+  int maxsb = 0;               // strong-branching LP capacity of the child buffers
+  int hw = 0;                  // best-first: pool high-water mark
+  size_t sort_bytes = 0;
+  int inherit = 0;             // longest path handed to children (<= the eta cap)
+  NodeHeap tree;               // order 2: the open nodes, their ids and pool slots
+  bool guided = true;          // IntVarHandler guided_dive (Environment.cpp:160-163)
+  std::vector<int> pick;       // mgpu_bnb_pick: pool slots of the picked nodes, in pick order
+  int carry = 0;               // clean-row masks: the mode at init, 0 when the tree cannot use them
+  size_t osort_bytes = 0;
 };
 
 void bnb_state_free(mgpu_ctx *c) {
-  if (c && c->bnb) {
-    c->bnb->release();
-    delete c->bnb;
-    c->bnb = nullptr;
-  }
+  if (!c) return;
+  delete c->bnb;
+  c->bnb = nullptr;
 }
 
 namespace {
@@ -363,14 +315,11 @@ int rel_round(mgpu_ctx *c, BnbState &s, int nb, int base, bool bfs) {
 
 // Reference-heap mode, after the round's scans: the host reads each node's
 // decision, bound, depth and branching choice, assigns pool slots to the
-// children (the round's own slots first, then older free slots, then new
-// ones), launches the children writer and pushes the children onto the heap
-// in the reference's branch order with the next node ids: the preferred
-// direction first, or — guided dive, with an incumbent — down first when the
-// incumbent's value of the variable is below the node's (IntVarHandler::
-// getBranches, IntVarHandler.cpp:125-175).
-int heap_children(mgpu_ctx *c, BnbState &s, BnbIO &io, int nb, const std::vector<uint32_t> &sel,
-                  const std::vector<HeapNode> &popped) {
+// children and the nodes modified by the brancher (NodeHeap::take_slot),
+// launches the children writer and pushes the children onto the heap in the
+// reference's branch order (down_first).
+int heap_children(mgpu_ctx *c, BnbState &s, BnbIO &io, int nb,
+                  const std::vector<NodeHeap::Node> &popped) {
   std::vector<int32_t> dec(nb), bvar(nb), dep(nb);
   std::vector<double> obj(nb), bval(nb);
   std::vector<int8_t> bup(nb);
@@ -381,41 +330,23 @@ int heap_children(mgpu_ctx *c, BnbState &s, BnbIO &io, int nb, const std::vector
   HIPCHK(c, hipMemcpyAsync(bval.data(), io.bval, (size_t)nb * 8, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipMemcpyAsync(bup.data(), io.bup, (size_t)nb, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  // free slots in the order children take them
-  std::vector<int> pool(sel.begin(), sel.end());
-  for (auto it = s.free_slots.rbegin(); it != s.free_slots.rend(); ++it) pool.push_back(*it);
-  s.free_slots.clear();
-  size_t next = 0;
-  auto take = [&]() -> int { return next < pool.size() ? pool[next++] : s.hw++; };
   std::vector<int32_t> cs;
-  struct Kid {
-    double lb;
-    int depth, slot, down;
-  };
-  std::vector<Kid> kids;
   for (int i = 0; i < nb; ++i) {
-    if (dec[i] != 0 && dec[i] != 5) continue;
-    if (dec[i] == 5) {
-      // ModifiedByBrancher: the same node (its id) is solved again right
-      // away with the bound change (PCBProcessor.cpp:295-310), ahead of
-      // the heap
-      const int sl = take();
+    if (dec[i] == 5) {   // ModifiedByBrancher: the same node again, with the bound change
+      const int sl = s.tree.take_slot();
       cs.push_back(sl);
-      s.front.push_back(HeapNode{obj[i], dep[i], popped[i].id, sl});
-      continue;
+      s.tree.requeue({obj[i], dep[i], popped[i].id, sl});
     }
-    const int s_pref = take(), s_other = take();   // child index p (preferred), p + 1
+    if (dec[i] != 0) continue;
+    const int s_pref = s.tree.take_slot(), s_other = s.tree.take_slot();   // child index p, p + 1
     cs.push_back(s_pref);
     cs.push_back(s_other);
     const bool pref_up = bup[i] != 0;
-    bool down_first = !pref_up;
-    if (s.guided && std::isfinite(s.inc) && !std::isnan(s.best_x[bvar[i]]))
-      down_first = s.best_x[bvar[i]] < bval[i];
-    const int s_down = pref_up ? s_other : s_pref, s_up = pref_up ? s_pref : s_other;
-    kids.push_back({obj[i], dep[i] + 1, down_first ? s_down : s_up, 0});
-    kids.push_back({obj[i], dep[i] + 1, down_first ? s_up : s_down, 0});
+    const bool pref_first =   // the preferred child is the up child exactly when pref_up
+        down_first(true, pref_up, s.guided, s.inc, s.best_x[bvar[i]], bval[i]) != pref_up;
+    s.tree.push(obj[i], dep[i] + 1, pref_first ? s_pref : s_other);
+    s.tree.push(obj[i], dep[i] + 1, pref_first ? s_other : s_pref);
   }
-  for (size_t k = next; k < pool.size(); ++k) s.free_slots.push_back(pool[k]);
   if (!cs.empty()) {
     HIPCHK(c, s.cslots.ensure(cs.size() * 4));
     HIPCHK(c, hipMemcpyAsync(s.cslots.p, cs.data(), cs.size() * 4, hipMemcpyHostToDevice,
@@ -423,11 +354,7 @@ int heap_children(mgpu_ctx *c, BnbState &s, BnbIO &io, int nb, const std::vector
     io.child_slots = s.cslots.as<int32_t>();
     HIPCHK(c, launch_bnb_children(io, s.n, c->stream));
   }
-  for (const Kid &k : kids) {
-    s.heap.push_back(HeapNode{k.lb, k.depth, s.next_id++, k.slot});
-    std::push_heap(s.heap.begin(), s.heap.end(), heap_greater);
-  }
-  s.count = (int)(s.heap.size() + s.front.size());
+  s.count = s.tree.open();
   return MGPU_OK;
 }
 
@@ -492,7 +419,7 @@ int mgpu_bnb_init(mgpu_ctx *c, int capacity, const double *root_lb, const double
   BnbState *s = new BnbState();
   if (c->bnb) {
     HIPCHK(c, hipStreamSynchronize(c->stream));   // the old tree's kernels are done with them
-    s->adopt(*c->bnb);
+    static_cast<BnbBufs &>(*s) = std::move(*c->bnb);
   }
   bnb_state_free(c);
   c->bnb = s;
@@ -597,9 +524,7 @@ int mgpu_bnb_init(mgpu_ctx *c, int capacity, const double *root_lb, const double
     HIPCHK(c, s->plive.ensure((size_t)capacity));
     HIPCHK(c, hipMemsetAsync(s->plive.p, 0, (size_t)capacity, c->stream));
     HIPCHK(c, s->vals2.ensure((size_t)capacity * 4));
-    s->heap.push_back(HeapNode{-INFINITY, 0, 0, 0});
-    s->next_id = 1;
-    s->hw = 1;
+    s->tree.reset(capacity);
     s->guided = c->bnb_guided;
   }
   if (s->order == 1) {
@@ -666,41 +591,22 @@ int mgpu_bnb_round(mgpu_ctx *c, int batch, double incumbent, mgpu_bnb_stats *sta
   const bool heap = s.order == 2;
   const bool root_round = heap && s.tot.rounds == 0;
   int nb, base = 0, live = 0, holes = 0;
-  std::vector<uint32_t> sel;
-  std::vector<HeapNode> popped;
+  std::vector<uint32_t> sel;   // (alive until the round's last synchronise)
+  NodeHeap::Round popped;
   if (heap) {
-    // nodes modified by the brancher first (their process() call goes on),
-    // then TreeManager::getCandidate: the heap top, pruned lazily by the
-    // incumbent (TreeManager::shouldPrune_, :403-413), then removed
-    size_t nf = 0;
-    for (; nf < s.front.size() && (int)sel.size() < batch; ++nf) {
-      sel.push_back((uint32_t)s.front[nf].slot);
-      popped.push_back(s.front[nf]);
-    }
-    s.front.erase(s.front.begin(), s.front.begin() + nf);
-    while ((int)sel.size() < batch && !s.heap.empty()) {
-      const HeapNode top = s.heap.front();
-      std::pop_heap(s.heap.begin(), s.heap.end(), heap_greater);
-      s.heap.pop_back();
-      if (top.lb > s.inc - 1e-6 || std::fabs(s.inc - top.lb) / (std::fabs(s.inc) + 1e-6) * 100.0 < 1e-6) {
-        s.free_slots.push_back(top.slot);
-        s.tot.pruned += 1;
-        continue;
-      }
-      sel.push_back((uint32_t)top.slot);
-      popped.push_back(top);
-    }
-    nb = (int)sel.size();
-    live = (int)(s.heap.size() + s.front.size()) + nb;
+    popped = s.tree.take(batch, s.inc);
+    s.tot.pruned += popped.pruned;
+    nb = (int)popped.nodes.size();
+    live = s.tree.open() + nb;
     s.count = live;
     if (nb <= 0) {
       s.tot.open = 0;
       if (stats) *stats = s.tot;
       return MGPU_OK;
     }
-    const long need = 2L * nb - nb - (long)s.free_slots.size();
-    if (s.hw + (need > 0 ? need : 0) > s.cap)
+    if (!popped.fits)
       return fail(c, MGPU_ERR_NOMEM, "mgpu_bnb_round: node pool full (%d slots)", s.cap);
+    for (const NodeHeap::Node &nd : popped.nodes) sel.push_back((uint32_t)nd.slot);
     HIPCHK(c, hipMemcpyAsync(s.vals2.p, sel.data(), (size_t)nb * 4, hipMemcpyHostToDevice,
                              c->stream));
   } else if (!bfs) {
@@ -944,7 +850,7 @@ int mgpu_bnb_round(mgpu_ctx *c, int batch, double incumbent, mgpu_bnb_stats *sta
   if (bfs) {
     io.slots = s.vals2.as<uint32_t>();
     io.live = live;
-    io.hw = s.hw;
+    io.hw = heap ? s.tree.hw() : s.hw;
     io.plive = s.plive.as<uint8_t>();
   }
   if (s.warm == 2) {  // children inherit the node's final basis
@@ -984,7 +890,7 @@ int mgpu_bnb_round(mgpu_ctx *c, int batch, double incumbent, mgpu_bnb_stats *sta
     HIPCHK(c, hipMemcpyAsync(rcnt, s.rcnt.p, sizeof rcnt, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   if (heap) {
-    rc = heap_children(c, s, io, nb, sel, popped);
+    rc = heap_children(c, s, io, nb, popped.nodes);
     if (rc != MGPU_OK) return rc;
   } else if (!bfs) {
     s.count = base + o.nchild;

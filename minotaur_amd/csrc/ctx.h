@@ -6,6 +6,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/mgpu.h"
@@ -29,6 +30,14 @@ struct DevBuf {
   DevBuf() = default;
   DevBuf(const DevBuf &) = delete;
   DevBuf &operator=(const DevBuf &) = delete;
+  // a move swaps: a struct of DevBufs is handed to the next tree in one
+  // assignment, and the old tree's destructor frees what came back
+  DevBuf(DevBuf &&o) noexcept { *this = std::move(o); }
+  DevBuf &operator=(DevBuf &&o) noexcept {
+    std::swap(p, o.p);
+    std::swap(bytes, o.bytes);
+    return *this;
+  }
   ~DevBuf() { release(); }
   hipError_t ensure(size_t want) {
     if (want <= bytes) return hipSuccess;

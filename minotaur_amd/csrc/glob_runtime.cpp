@@ -35,33 +35,31 @@
 
 #include "ctx.h"
 #include "glob_internal.h"
+#include "node_heap.h"
 #include "quad_state.h"
 
-// Reference node order (mgpu_glob_config order 2): TreeManager's "bfs"
-// NodeHeap (NodeHeap.cpp:24-47: bound within 1e-6, shallower first, then the
-// larger node id on top), node ids as TreeManager assigns them (root 0,
-// children in branch order, TreeManager.cpp:97-136), open nodes pruned at
-// the top by the incumbent (TreeManager::getCandidate, :162-186) -- the
-// batched linear tree's order 2 (bnb.cpp).
-struct GHeap {
-  double lb;
-  int depth;
-  long long id;
-  int slot;
+// The device buffers sized by the round (ensure_glob_batch; every use is
+// behind an ensure of its own size) and nothing else: the next tree of the
+// same context takes the whole struct over, so a tree at a batch seen before
+// allocates nothing inside a round.  Pool-sized and problem-sized buffers
+// stay with GlobState.
+struct GlobRoundBufs {
+  DevBuf wlb, wub, wrows, kinf, knm, st, obj, it, x, cand, dec, bvar, bval, bup, bint, pos,
+      depth_in, out;
+  DevBuf wvals, flag, skip2, st2, obj2, it2, x2, acc;   // the separation loop
+  DevBuf gsel, cslots, glb, gub, grows, gtan, gdepth, ghead, gst, gok, skip_a;
+  DevBuf wo_head, wo_st, wo_d, wo_binv;            // the round's optimal bases
+  DevBuf flb, fub, finf, fflag;                    // the linear presolve's scratch
+  // the lockstep: the per-node device state of glob_rel.hip in one buffer
+  // sized by the widest round (rs_carve)
+  DevBuf rs_buf;
 };
-static bool gheap_greater(const GHeap &a, const GHeap &b) {
-  if (a.lb > b.lb + 1e-6) return true;
-  if (a.lb < b.lb - 1e-6) return false;
-  if (a.depth < b.depth) return false;
-  if (a.depth > b.depth) return true;
-  return a.id < b.id;
-}
 
-struct GlobState {
+struct GlobState : GlobRoundBufs {
   int nv = 0, R = 0, S = 0, T = 0, cap = 0, count = 0, maxb = 0;
-  // mgpu_glob_config at init: order 0 stack / 2 reference heap; warm 0 the
-  // root basis / 1 the parent's basis; qt 1 tightenQuad_ at every node / 0 at
-  // the first presolveNode call only
+  // mgpu_glob_config at init: order 0 stack / 2 reference heap (node_heap.h);
+  // warm 0 the root basis / 1 the parent's basis; qt 1 tightenQuad_ at every
+  // node / 0 at the first presolveNode call only
   int order = 0, warm = 0, qt = 1, lin = 0, obbt = 0;
   mgpu_ctx *bte = nullptr;       // root OBBT's bound-tightening engine (bte_)
   // Glob's relstronger (mgpu_glob_brancher 1, 2): per pool slot the branching
@@ -79,9 +77,7 @@ struct GlobState {
     double value;
   };
   std::vector<LpRec> lp_log;     // relstronger: every main-engine solve in order
-  // the lockstep: the per-node device state of glob_rel.hip in one buffer
-  // sized by the widest round (rs_carve), and the host's staging of a round
-  DevBuf rs_buf;
+  // the lockstep: the host's staging of a round
   std::vector<RsNode> rs_hnode;
   std::vector<RsObs> rs_hobs;
   std::vector<std::vector<LpRec>> rs_nlog;   // the round's solves per node
@@ -89,76 +85,34 @@ struct GlobState {
   std::vector<char> rs_blk;
   std::vector<double> rs_hpc;
   std::vector<int32_t> rs_htm, rs_hcs;
-  std::vector<GHeap> heap;
-  std::vector<int> free_slots;
-  long long next_id = 1;
-  int hw = 0;                    // reference order: pool high-water mark
+  NodeHeap tree;                 // order 2: the open nodes, their ids and pool slots
   DevBuf pws_head, pws_st, pws_ok;                 // per pool slot: the parent's basis
-  DevBuf gsel, cslots, glb, gub, grows, gtan, gdepth, ghead, gst, gok, skip_a;
-  DevBuf wo_head, wo_st, wo_d, wo_binv;            // the round's optimal bases
   double inc = INFINITY;
   bool root_ws = false;
   std::vector<double> best_x;
   mgpu_glob_stats tot{};
   DevBuf plb, pub, prows, pnlb, pdepth, ptan;
-  DevBuf wlb, wub, wrows, kinf, knm, st, obj, it, x, cand, dec, bvar, bval, bup, bint, pos,
-      depth_in, out;
-  DevBuf wvals, flag, skip2, st2, obj2, it2, x2, acc;   // the separation loop
   DevBuf ws_head, ws_st, ws_d, ws_binv, r_st, r_obj, r_it;
   DevBuf fvtype, fsq, fbil, flptr, flvar, flval, fqptr, fqv1, fqv2, fqval, fclb, fcub;
-  // the linear presolve (lin 1): the relaxation's term table and its scratch
+  // the linear presolve (lin 1): the relaxation's term table
   int M = 0, nobj = 0, cons_bad = 0;
   std::vector<int32_t> h_rptr, h_tvar, h_tsrc, h_rhsrc, h_oidx;
   std::vector<double> h_tval, h_rlo, h_rhi, h_oval;
   DevBuf lrptr, ltvar, ltsrc, ltrow, lrhsrc, lcptr, lcterm, loidx, ltval, lrlo, lrhi, loval;
-  DevBuf flb, fub, finf, fflag;
-  void release() {
-    for (DevBuf *b : {&plb, &pub, &prows, &pnlb, &pdepth, &ptan, &wlb, &wub, &wrows, &kinf,
-                      &knm, &st, &obj, &it, &x, &cand, &dec, &bvar, &bval, &bup, &bint, &pos,
-                      &depth_in, &out, &wvals, &flag, &skip2, &st2, &obj2, &it2, &x2, &acc,
-                      &ws_head, &ws_st, &ws_d, &ws_binv, &r_st, &r_obj, &r_it, &fvtype, &fsq,
-                      &fbil, &flptr, &flvar, &flval, &fqptr, &fqv1, &fqv2, &fqval, &fclb, &fcub,
-                      &pws_head, &pws_st, &pws_ok, &gsel, &cslots, &glb, &gub, &grows, &gtan,
-                      &gdepth, &ghead, &gst, &gok, &skip_a, &wo_head, &wo_st, &wo_d, &wo_binv,
-                      &lrptr, &ltvar, &ltsrc, &ltrow, &lrhsrc, &lcptr, &lcterm, &loidx, &ltval,
-                      &lrlo, &lrhi, &loval, &flb, &fub, &finf, &fflag, &rs_buf})
-      b->release();
+  ~GlobState() {
     if (bte) mgpu_destroy(bte);
-    bte = nullptr;
   }
-  // The next tree of the same context takes over the buffers sized by the
-  // round (ensure_glob_batch; every use is behind an ensure of its own size)
-  // and the OBBT engine, so a tree at a batch seen before allocates nothing
-  // inside a round.
-  void adopt_round_buffers(GlobState &old) {
-    DevBuf *mine[] = {&wlb, &wub, &wrows, &x, &cand, &kinf, &knm, &st, &it, &dec, &bvar, &pos,
-                      &depth_in, &obj, &bval, &bup, &bint, &out, &wvals, &flag, &skip2, &st2,
-                      &it2, &skip_a, &obj2, &x2, &acc, &gsel, &cslots, &glb, &gub, &grows, &gtan,
-                      &gdepth, &ghead, &gst, &gok, &wo_head, &wo_st, &wo_d, &wo_binv, &flb, &fub,
-                      &finf, &fflag, &rs_buf};
-    DevBuf *theirs[] = {&old.wlb, &old.wub, &old.wrows, &old.x, &old.cand, &old.kinf, &old.knm,
-                        &old.st, &old.it, &old.dec, &old.bvar, &old.pos, &old.depth_in, &old.obj,
-                        &old.bval, &old.bup, &old.bint, &old.out, &old.wvals, &old.flag,
-                        &old.skip2, &old.st2, &old.it2, &old.skip_a, &old.obj2, &old.x2, &old.acc,
-                        &old.gsel, &old.cslots, &old.glb, &old.gub, &old.grows, &old.gtan,
-                        &old.gdepth, &old.ghead, &old.gst, &old.gok, &old.wo_head, &old.wo_st,
-                        &old.wo_d, &old.wo_binv, &old.flb, &old.fub, &old.finf, &old.fflag,
-                        &old.rs_buf};
-    static_assert(sizeof mine == sizeof theirs, "the same buffers on both sides");
-    for (size_t k = 0; k < sizeof mine / sizeof mine[0]; ++k) {
-      std::swap(mine[k]->p, theirs[k]->p);
-      std::swap(mine[k]->bytes, theirs[k]->bytes);
-    }
+  // the round-sized buffers and the OBBT engine of the context's last tree
+  void adopt(GlobState &old) {
+    static_cast<GlobRoundBufs &>(*this) = std::move(old);
     std::swap(bte, old.bte);
   }
 };
 
 void glob_state_free(mgpu_ctx *c) {
-  if (c && c->glob) {
-    c->glob->release();
-    delete c->glob;
-    c->glob = nullptr;
-  }
+  if (!c) return;
+  delete c->glob;
+  c->glob = nullptr;
 }
 
 namespace {
@@ -703,8 +657,8 @@ int glob_obbt_node0(mgpu_ctx *c, GlobState &s, const GlobIO &io, bool *changed, 
 // optimal or at the iteration limit becoming the next solve's start, as the
 // reference's one engine chains it.  The root's round (always one node) runs
 // root OBBT between the root's first decision and its separation.
-int glob_rs_lockstep(mgpu_ctx *c, GlobState &s, GlobIO &io, const std::vector<GHeap> &popped,
-                     mgpu_glob_stats *stats) {
+int glob_rs_lockstep(mgpu_ctx *c, GlobState &s, GlobIO &io,
+                     const std::vector<NodeHeap::Node> &popped, mgpu_glob_stats *stats) {
   const int nb = io.nb, nv = s.nv, T = s.T, m = c->lp.m, N = nv + m;
   hipStream_t stream = c->stream;
   size_t total = 0;
@@ -846,7 +800,7 @@ int glob_rs_lockstep(mgpu_ctx *c, GlobState &s, GlobIO &io, const std::vector<GH
   const double *objv = reinterpret_cast<const double *>(s.rs_blk.data());
   for (const RsObs &ob : s.rs_hobs) s.rs_nobs[(size_t)ob.node].push_back(ob);   // (in the order made)
   s.rs_hcs.assign((size_t)nb * 2, -1);
-  std::vector<GHeap> kids;
+  bool kids = false;
   long long ndec4 = 0;
   for (int b = 0; b < nb; ++b) {
     const RsNode &n = s.rs_hnode[(size_t)b];
@@ -876,25 +830,13 @@ int glob_rs_lockstep(mgpu_ctx *c, GlobState &s, GlobIO &io, const std::vector<GH
     // the children (QuadHandler::getBranches down, up; IntVarHandler's guided
     // dive on the round-start incumbent, else the candidate's direction)
     const int j = n.o_var;
-    const bool isint = n.o_isint != 0, up_first = n.o_dir != 0;
-    bool down_first = true;
-    if (isint) {
-      down_first = !up_first;
-      if (std::isfinite(inc0) && !std::isnan(bx0[(size_t)j])) down_first = bx0[(size_t)j] < n.o_v;
-    }
+    const bool isint = n.o_isint != 0;
+    const bool df = down_first(isint, n.o_dir != 0, true, inc0, bx0[(size_t)j], n.o_v);
     if (isint) s.tot.br_int += 1;
     else s.tot.br_cont += 1;
     for (int k = 0; k < 2; ++k) {
-      const bool upc = down_first ? k == 1 : k == 0;
-      int slot;
-      if (!s.free_slots.empty()) {
-        slot = s.free_slots.back();
-        s.free_slots.pop_back();
-      } else {
-        if (s.hw >= s.cap)
-          return fail(c, MGPU_ERR_NOMEM, "mgpu_glob_round: node pool full (%d slots)", s.cap);
-        slot = s.hw++;
-      }
+      const bool upc = df ? k == 1 : k == 0;
+      const int slot = s.tree.take_slot();
       s.rs_hcs[(size_t)(2 * b + (upc ? 1 : 0))] = slot;
       GlobState::BrInfo bi;
       bi.var = j;
@@ -904,21 +846,18 @@ int glob_rs_lockstep(mgpu_ctx *c, GlobState &s, GlobIO &io, const std::vector<GH
       bi.ud = n.o_ud;
       bi.plb = n.objval;
       s.pinfo[(size_t)slot] = bi;
-      kids.push_back(GHeap{n.objval, popped[(size_t)b].depth + 1, s.next_id++, slot});
+      s.tree.push(n.objval, popped[(size_t)b].depth + 1, slot);
+      kids = true;
     }
   }
-  if (!kids.empty()) {
+  if (kids) {
     HIPCHK(c, hipMemcpyAsync(s.cslots.p, s.rs_hcs.data(), (size_t)nb * 8, hipMemcpyHostToDevice,
                              stream));
     rs.cs = s.cslots.as<int32_t>();
     HIPCHK(c, launch_rs_children(io, rs, stream));
     HIPCHK(c, hipStreamSynchronize(stream));
   }
-  for (const GHeap &k : kids) {
-    s.heap.push_back(k);
-    std::push_heap(s.heap.begin(), s.heap.end(), gheap_greater);
-  }
-  s.count = (int)s.heap.size();
+  s.count = s.tree.open();
   s.tot.rounds += 1;
   s.tot.nodes += nb;
   s.tot.cuts += cuts;
@@ -976,7 +915,7 @@ int mgpu_glob_init(mgpu_ctx *c, int capacity, double incumbent) {
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   GlobState *s = new GlobState();
-  if (c->glob) s->adopt_round_buffers(*c->glob);
+  if (c->glob) s->adopt(*c->glob);
   glob_state_free(c);
   c->glob = s;
   const int nv = q.nv, R = q.R, m = c->lp.m, N = nv + m;
@@ -1048,9 +987,7 @@ int mgpu_glob_init(mgpu_ctx *c, int capacity, double incumbent) {
   }
   s->count = 1;
   if (s->order == 2) {   // the root is node 0 in slot 0
-    s->heap.push_back(GHeap{-INFINITY, 0, 0, 0});
-    s->next_id = 1;
-    s->hw = 1;
+    s->tree.reset(capacity);
   }
   if (s->warm == 1) {    // per slot: the parent's basis; the root has none (slack basis)
     HIPCHK(c, s->pws_head.ensure((size_t)capacity * m * 4));
@@ -1096,26 +1033,12 @@ int mgpu_glob_round(mgpu_ctx *c, int batch, double incumbent, mgpu_glob_stats *s
   const int nv = s.nv, R = s.R, m = c->lp.m, N = nv + m;
   int nb = 0, base = 0;
   std::vector<int32_t> sel;
-  std::vector<GHeap> popped;
+  NodeHeap::Round round;
   if (heap) {
-    // TreeManager::getCandidate: the heap top, pruned lazily by the
-    // incumbent (TreeManager::shouldPrune_, :403-413)
-    while ((int)sel.size() < batch && !s.heap.empty()) {
-      const GHeap top = s.heap.front();
-      std::pop_heap(s.heap.begin(), s.heap.end(), gheap_greater);
-      s.heap.pop_back();
-      if (top.lb > s.inc - 1e-6 ||
-          std::fabs(s.inc - top.lb) / (std::fabs(s.inc) + 1e-6) * 100.0 < 1e-6) {
-        s.free_slots.push_back(top.slot);
-        continue;
-      }
-      sel.push_back(top.slot);
-      popped.push_back(top);
-    }
+    round = s.tree.take(batch, s.inc);
+    for (const NodeHeap::Node &nd : round.nodes) sel.push_back(nd.slot);
     nb = (int)sel.size();
-    // children: two per node in the round's own slots, the free ones, then new
-    const long need = (long)nb - (long)s.free_slots.size();
-    if (nb > 0 && s.hw + (need > 0 ? need : 0) > s.cap)
+    if (!round.fits)
       return fail(c, MGPU_ERR_NOMEM, "mgpu_glob_round: node pool full (%d slots)", s.cap);
   } else {
     nb = batch < s.count ? batch : s.count;
@@ -1214,7 +1137,6 @@ int mgpu_glob_round(mgpu_ctx *c, int batch, double incumbent, mgpu_glob_stats *s
     io.gtan = s.gtan.as<double>();
     io.gdepth = s.gdepth.as<int32_t>();
     HIPCHK(c, launch_glob_gather(io, c->stream));
-    for (int32_t sl : sel) s.free_slots.push_back(sl);   // the round's slots are free now
     in_lb = io.glb;
     in_ub = io.gub;
     in_rows = io.grows;
@@ -1299,7 +1221,7 @@ int mgpu_glob_round(mgpu_ctx *c, int batch, double incumbent, mgpu_glob_stats *s
     // same x and bases, merged by flag
     bool cold = !heap;
     if (heap)
-      for (const GHeap &g : popped) cold |= g.id == 0;
+      for (const NodeHeap::Node &g : round.nodes) cold |= g.id == 0;
     if (cold) {
       rc = solve(io.skip2, nullptr, nullptr, 1, nullptr, s.st2.as<int32_t>(), s.obj2.as<double>(),
                  s.it2.as<int32_t>(), s.x.as<double>());
@@ -1318,7 +1240,7 @@ int mgpu_glob_round(mgpu_ctx *c, int batch, double incumbent, mgpu_glob_stats *s
   HIPCHK(c, launch_glob_decide(io, c->stream));
   // relstronger: the round's nodes through PCBProcessor::process's loop in
   // lockstep (kind 1: batch is 1, the reference's node at a time)
-  if (s.brancher >= 1) return glob_rs_lockstep(c, s, io, popped, stats);
+  if (s.brancher >= 1) return glob_rs_lockstep(c, s, io, round.nodes, stats);
   // the flagged nodes (flag / skip2) re-solved -- from the root basis (warm
   // 0) or the node's last basis refactored for its rows (warm 1) -- merged
   // back and decided again
@@ -1382,10 +1304,7 @@ int mgpu_glob_round(mgpu_ctx *c, int batch, double incumbent, mgpu_glob_stats *s
   HIPCHK(c, launch_glob_summary(io, c->stream));
   GlobOut o;
   if (heap) {
-    // the children in the reference's branch order: QuadHandler::getBranches
-    // down then up (QuadHandler.cpp:422-471); IntVarHandler::getBranches the
-    // guided dive's side first with an incumbent, else the candidate's
-    // preferred direction (IntVarHandler.cpp:133-190)
+    // the children in the reference's branch order (down_first)
     std::vector<int32_t> dec(nb), bvar(nb), pos(nb), dep(nb);
     std::vector<double> obj(nb), bval(nb);
     std::vector<int8_t> bup(nb), bint(nb);
@@ -1404,42 +1323,23 @@ int mgpu_glob_round(mgpu_ctx *c, int batch, double incumbent, mgpu_glob_stats *s
     // pool before the next node branches; at batch 1 no other node shares
     // the round)
     std::vector<int32_t> cs((size_t)o.nchild);
-    size_t nfree = 0;
-    auto take = [&]() -> int {
-      if (nfree < s.free_slots.size()) return s.free_slots[nfree++];
-      return s.hw++;
-    };
-    struct Kid {
-      double lb;
-      int depth, slot;
-    };
-    std::vector<Kid> kids;
     for (int i = 0; i < nb; ++i) {
       if (dec[i] != 0) continue;
-      const int s_down = take(), s_up = take();
+      const int s_down = s.tree.take_slot(), s_up = s.tree.take_slot();
       cs[(size_t)pos[i]] = s_down;
       cs[(size_t)pos[i] + 1] = s_up;
-      bool down_first = true;
-      if (bint[i]) {
-        down_first = bup[i] == 0;
-        if (std::isfinite(s.inc) && !std::isnan(s.best_x[(size_t)bvar[i]]))
-          down_first = s.best_x[(size_t)bvar[i]] < bval[i];
-      }
-      kids.push_back({obj[i], dep[i] + 1, down_first ? s_down : s_up});
-      kids.push_back({obj[i], dep[i] + 1, down_first ? s_up : s_down});
+      const bool df = down_first(bint[i] != 0, bup[i] != 0, true, s.inc,
+                                 s.best_x[(size_t)bvar[i]], bval[i]);
+      s.tree.push(obj[i], dep[i] + 1, df ? s_down : s_up);
+      s.tree.push(obj[i], dep[i] + 1, df ? s_up : s_down);
     }
-    s.free_slots.erase(s.free_slots.begin(), s.free_slots.begin() + (long)nfree);
     if (!cs.empty()) {
       HIPCHK(c, hipMemcpyAsync(s.cslots.p, cs.data(), cs.size() * 4, hipMemcpyHostToDevice,
                                c->stream));
       io.child_slots = s.cslots.as<int32_t>();
       HIPCHK(c, launch_glob_children(io, c->stream));
     }
-    for (const Kid &k : kids) {
-      s.heap.push_back(GHeap{k.lb, k.depth, s.next_id++, k.slot});
-      std::push_heap(s.heap.begin(), s.heap.end(), gheap_greater);
-    }
-    s.count = (int)s.heap.size();
+    s.count = s.tree.open();
   } else {
     HIPCHK(c, launch_glob_children(io, c->stream));
     HIPCHK(c, hipMemcpyAsync(&o, s.out.p, sizeof o, hipMemcpyDeviceToHost, c->stream));

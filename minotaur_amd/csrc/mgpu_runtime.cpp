@@ -56,17 +56,6 @@ int mgpu_destroy(mgpu_ctx *c) {
   if (!c) return MGPU_ERR_ARG;
   (void)hipSetDevice(c->device);
   (void)hipStreamSynchronize(c->stream);
-  for (DevBuf *b : {&c->rowptr, &c->terms, &c->rlo, &c->rhi, &c->colptr, &c->rowidx,
-                    &c->vtype, &c->obj, &c->collb, &c->colub, &c->objd, &c->rows,
-                    &c->trec, &c->orec, &c->irec, &c->ccont, &c->cval, &c->ccol, &c->rval,
-                    &c->lp_lb, &c->lp_ub, &c->lp_skip, &c->lp_wh, &c->lp_wst, &c->lp_wd,
-                    &c->lp_wb, &c->lp_st, &c->lp_obj, &c->lp_it, &c->lp_x, &c->lp_oh,
-                    &c->lp_ost, &c->lp_od, &c->lp_ob, &c->lp_slots, &c->io_lb_in,
-                    &c->io_ub_in, &c->io_lb_out, &c->io_ub_out, &c->io_inf, &c->io_nmods,
-                    &c->io_mv, &c->io_ml, &c->io_mval, &c->scratch, &c->flag_scratch,
-                    &c->fbbt_next, &c->lp_next3, &c->nr_map, &c->nr_ws, &c->nr_vals, &c->pfi_piv,
-                    &c->colmask})
-    b->release();
   for (auto &ch : c->ws_chunks)
     if (ch.base) (void)hipFree(ch.base);
   c->ws_chunks.clear();

@@ -20,22 +20,15 @@ struct QpState {
   DevBuf h_l, h_u, h_st, h_obj, h_it, h_x;  // host-path device copies
   DevBuf f_mask, f_st, f_obj, f_it;          // the tree's feasibility LPs
   std::vector<hipEvent_t> kev;               // mgpu_set_qp_ktime: 4 per iteration
-  void release() {
+  ~QpState() {
     for (hipEvent_t e : kev) (void)hipEventDestroy(e);
-    kev.clear();
-    for (DevBuf *p : {&Q, &c, &A, &AT, &b, &l, &u, &x, &zl, &zu, &y, &rd, &rp, &K, &W, &WT, &M,
-                      &done, &iters, &status, &obj, &h_l, &h_u, &h_st, &h_obj, &h_it, &h_x,
-                      &f_mask, &f_st, &f_obj, &f_it})
-      p->release();
   }
 };
 
 void qp_state_free(mgpu_ctx *c) {
-  if (c && c->qp) {
-    c->qp->release();
-    delete c->qp;
-    c->qp = nullptr;
-  }
+  if (!c) return;
+  delete c->qp;
+  c->qp = nullptr;
 }
 
 namespace {

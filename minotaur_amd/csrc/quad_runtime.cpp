@@ -20,11 +20,9 @@
 #include "quad_state.h"
 
 void quad_state_free(mgpu_ctx *c) {
-  if (c && c->quad) {
-    c->quad->release();
-    delete c->quad;
-    c->quad = nullptr;
-  }
+  if (!c) return;
+  delete c->quad;
+  c->quad = nullptr;
 }
 
 namespace {

@@ -19,11 +19,5 @@ struct QuadState {
   DevBuf vtype, sq, bil, fun[2], term[2];
   DevBuf io_lb_in, io_ub_in, io_lb_out, io_ub_out, io_rin, io_rout, io_inf, io_nm, io_kind,
       io_idx, io_v1, io_v2, scratch;
-  void release() {
-    for (DevBuf *b : {&vtype, &sq, &bil, &fun[0], &fun[1], &term[0], &term[1], &io_lb_in,
-                      &io_ub_in, &io_lb_out, &io_ub_out, &io_rin, &io_rout, &io_inf, &io_nm,
-                      &io_kind, &io_idx, &io_v1, &io_v2, &scratch})
-      b->release();
-  }
 };
 

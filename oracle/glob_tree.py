@@ -330,8 +330,8 @@ def separate(qp, x, tan, R, S):
 
 
 class _Heap:
-    """TreeManager's bfs NodeHeap order (NodeHeap.cpp:24-47, as
-    glob_runtime.cpp's gheap_greater): the smallest bound within 1e-6 on top,
+    """TreeManager's bfs NodeHeap order (NodeHeap.cpp:24-47, as the
+    comparator of csrc/node_heap.h): the smallest bound within 1e-6 on top,
     then the shallower node, then the larger id."""
 
     def __init__(self):

@@ -124,6 +124,28 @@ def test_reference_order_in_batches_proves_optimum(integ, ctx, batch):
     assert gpu["open"] == 0 and gpu["ub"] == ref["ub"]
 
 
+def test_trees_of_other_orders_hand_their_buffers_on():
+    """One context, three trees of one problem: reference order, depth-first,
+    reference order again.  Each proves the HiGHS optimum, and the third finds
+    every device buffer of the first still there, through the tree between
+    them that never touched most of them: it allocates nothing."""
+    from minotaur_amd.runtime import Context, alloc_stats
+    p = _cases()['mkp-12-2']
+    hs, hobj = oracle.highs_milp(p)
+    assert hs == 0
+    c = Context(0)
+    try:
+        c.load(p)
+        for k, (order, warm) in enumerate([(2, 1), (0, 0), (2, 1)]):
+            a0 = alloc_stats()
+            obj, _, st, _ = bnb.solve(c, batch=4, capacity=1 << 12, order=order, warm=warm)
+            assert st.open == 0 and abs(obj - hobj) <= 1e-6 * max(1.0, abs(hobj)), (k, obj, hobj)
+            if k == 2:
+                assert alloc_stats() == a0
+    finally:
+        c.close()
+
+
 def test_gpu_fbbt_handler_same_reference_tree(integ):
     """The reference tree with HipLinearHandler (K1 at B = 1 inside the
     reference) is the same tree as with the reference's own LinearHandler."""
