@@ -186,21 +186,25 @@ def solve_tree(ctx, qp: QpProblem, batch=1024, capacity=None, max_rounds=10**9, 
         ctx.bnb_relaxation(0)
 
 
-def random_miqp(seed: int, nbin: int = 8, ncont: int = 4, m: int = 2) -> QpProblem:
-    """A small convex MIQP whose optimum brute force over the binaries can
-    check: binaries x, continuous y in [0, 2], rows sum_j a_ij x_j +
-    sum_k c_ik y_k = b_i (some binary assignments infeasible), Q = G G'/n +
-    0.01 I."""
+def random_miqp(seed: int, nbin: int = 8, ncont: int = 4, m: int = 2, nint: int = 0,
+                iub: int = 3) -> QpProblem:
+    """A small convex MIQP whose optimum brute force over the integer columns
+    can check: binaries x, then nint general integers z in [0, iub], then
+    continuous y in [0, 2], rows sum_j a_ij x_j + sum_j a_ij z_j + sum_k c_ik
+    y_k = b_i with b_i = 0.4 sum_j a_ij u_j over the integer columns + 0.7
+    sum_k c_ik (some integer assignments infeasible), Q = G G'/n + 0.01 I."""
     rng = np.random.default_rng(seed)
-    n = nbin + ncont
+    ni = nbin + nint
+    n = ni + ncont
     G = rng.normal(size=(n, n))
     Q = G @ G.T / n + 0.01 * np.eye(n)
     c = rng.normal(size=n)
     A = np.zeros((m, n))
-    A[:, :nbin] = rng.uniform(0.5, 1.5, size=(m, nbin)) * (rng.random((m, nbin)) < 0.6)
-    A[:, nbin:] = rng.uniform(0.5, 1.5, size=(m, ncont))
-    b = A[:, :nbin].sum(axis=1) * 0.4 + A[:, nbin:].sum(axis=1) * 0.7
+    A[:, :ni] = rng.uniform(0.5, 1.5, size=(m, ni)) * (rng.random((m, ni)) < 0.6)
+    A[:, ni:] = rng.uniform(0.5, 1.5, size=(m, ncont))
     l = np.zeros(n)
-    u = np.concatenate([np.ones(nbin), np.full(ncont, 2.0)])
-    vtype = np.array([0] * nbin + [4] * ncont, dtype=np.int32)   # Binary, Continuous
+    u = np.concatenate([np.ones(nbin), np.full(nint, float(iub)), np.full(ncont, 2.0)])
+    b = (A[:, :ni] * u[:ni]).sum(axis=1) * 0.4 + A[:, ni:].sum(axis=1) * 0.7
+    # Binary, Integer, Continuous
+    vtype = np.array([0] * nbin + [1] * nint + [4] * ncont, dtype=np.int32)
     return QpProblem(f'miqp{seed}', Q, c, 0.0, A, b, l, u, vtype)

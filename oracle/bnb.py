@@ -21,7 +21,15 @@ children), same pool order:
 * brancher 0: MaxVioBrancher; brancher 1: the batched ReliabilityBrancher of
   bnb_rel.hip (pseudocosts frozen at the round's start plus each node's own
   updateAfterSolve observation, strong-branching LPs from each node's optimal
-  basis with iteration limit 25, observations folded in node order).
+  basis with iteration limit 25, observations folded in node order);
+* relaxation 1 (mgpu_bnb_relaxation): the node relaxation is the loaded QP
+  (load_qp) and the problem its rows (qp.rows_problem).  A round is K1 without
+  an incumbent, oracle/qp_ipm.py on the tightened boxes K1 left standing, the
+  phase-1 LP of qp_runtime.cpp for nodes the interior point left at status 6,
+  then the same decisions, children and pool order as for LPs (orders 0 and
+  1, warm 0, MaxVio).  Such a tree also records how far its decisions were
+  from their thresholds (``margins``) and every box it handed to the interior
+  point (``ipm``).
 
 ``CpuBnbContext`` exposes the engine's bnb_* methods so minotaur_amd.bnb's
 drivers run unchanged on it (gloo tests of the multi-rank control flow, and
@@ -60,12 +68,13 @@ def _order_key(v):
 
 
 class _Node:
-    __slots__ = ('lb', 'ub', 'nlb', 'depth', 'ws', 'pvar', 'pval', 'path')
+    __slots__ = ('lb', 'ub', 'nlb', 'depth', 'ws', 'pvar', 'pval', 'path', 'pid')
 
     def __init__(self, lb, ub, nlb, depth, ws=None, pvar=-1, pval=0.0, path=None):
         self.lb, self.ub, self.nlb, self.depth, self.ws = lb, ub, nlb, depth, ws
         self.pvar, self.pval = pvar, pval
         self.path = path    # warm 2: (k, pivots, statuses) or None = the root basis
+        self.pid = None     # QP trees: the parent's number (siblings share it)
 
 
 # ReliabilityBrancher defaults (ReliabilityBrancher.cpp:43-58)
@@ -91,6 +100,25 @@ class CpuBnbContext:
         self.order, self.warm = order, warm
         self.brancher = brancher
         self.grow_next = 0
+        self.relax_next = 0
+        self.qp = None
+
+    def load_qp(self, qp, cache=None):
+        """mgpu_load_qp: ``qp`` has the columns of the problem, which is its
+        rows (qp.rows_problem).  ``cache`` (a dict) keeps the interior point's
+        answer per node box, for trees over the same QP that meet the same
+        boxes."""
+        if qp.n != self.problem.n:
+            raise ValueError('load_qp: the QP and the loaded rows differ in their columns')
+        self.qp = qp
+        self.qp_cache = {} if cache is None else cache
+
+    def bnb_relaxation(self, kind):
+        """mgpu_bnb_relaxation: the next tree's node relaxation, 0 the LP, 1
+        the loaded QP."""
+        if int(kind) not in (0, 1):
+            raise ValueError('bnb_relaxation: 0 (LP) or 1 (the loaded QP)')
+        self.relax_next = int(kind)
 
     def bnb_config(self, order=0, warm=0):
         self.order, self.warm = int(order), int(warm)
@@ -108,7 +136,21 @@ class CpuBnbContext:
         lb = np.array(p.vlb if root_lb is None else root_lb, dtype=np.float64)
         ub = np.array(p.vub if root_ub is None else root_ub, dtype=np.float64)
         self.cap = capacity
-        st, obj, x, y, it, ws = oracle.dual_simplex_root(p, lb, ub, iter_limit=10000)
+        self.relax = self.relax_next
+        if self.relax:
+            if self.qp is None or self.warm != 0 or self.brancher != 0 or self.order > 1:
+                raise ValueError('bnb_init: QP relaxations need load_qp, root warm starts '
+                                 '(warm 0), MaxVio branching and order 0 or 1')
+            st, ws = -1, None      # no LP basis to share
+            self.margins = dict(intg=math.inf, prune=math.inf, score=math.inf, dir=math.inf,
+                                select=math.inf)
+            self.ipm = []          # per node handed to the interior point, in tree order
+            self.nskip = self.nsettled = self.nstatus12 = self.nsolved = 0
+            self.nparents = 0
+            self.max_batch = 0
+            self.int_branch = 0    # branchings with floor(value) >= 1
+        else:
+            st, obj, x, y, it, ws = oracle.dual_simplex_root(p, lb, ub, iter_limit=10000)
         self.ws = ws if st == 0 else None
         self.pool = [_Node(lb, ub, -math.inf, 0, self.ws)]   # stack, or slots (None = free)
         self.inc = incumbent
@@ -132,6 +174,10 @@ class CpuBnbContext:
             if nd is None:
                 continue
             lb = float(nd.nlb)
+            if self.relax and math.isfinite(inc) and math.isfinite(lb):
+                # an open node's distance to the two tests of the pool's pruning rule
+                self._margin('prune', abs(lb - (inc - 1e-6)))
+                self._margin('prune', abs(abs(inc - lb) - 1e-8 * (abs(inc) + 1e-6)))
             if lb > inc - 1e-6 or abs(inc - lb) / (abs(inc) + 1e-6) * 100.0 < 1e-6:
                 self.pool[i] = None
                 self.tot.pruned += 1
@@ -139,6 +185,14 @@ class CpuBnbContext:
                       key=lambda i: (_order_key(self.pool[i].nlb), i))
         holes = [i for i, nd in enumerate(self.pool) if nd is None]
         nb = min(batch, len(live))
+        if self.relax:
+            # the gaps between the different bounds that order the round's nodes
+            # (siblings carry the same bits on either side and are ordered by
+            # their slots; an exact tie of two other nodes counts as a gap of 0)
+            for a, b in zip(live[:nb], live[1:nb + 1]):
+                na, nb_ = self.pool[a], self.pool[b]
+                if math.isfinite(na.nlb) and (na.pid is None or na.pid != nb_.pid):
+                    self._margin('select', float(nb_.nlb) - float(na.nlb))
         sel = live[:nb]
         nodes = [self.pool[i] for i in sel]
         for i in sel:
@@ -169,13 +223,20 @@ class CpuBnbContext:
                 return self.tot
         LB = np.stack([nd.lb for nd in nodes])
         UB = np.stack([nd.ub for nd in nodes])
-        f = oracle.linear_fbbt(p, LB, UB, self.inc if math.isfinite(self.inc) else None)
+        # LinearHandler::varBndsFromObj_ propagates a linear objective only: the
+        # QP's objective is quadratic, so its node FBBT runs without the
+        # incumbent (FBBT skips an objective without nonzeros by itself; the
+        # incumbent would bite only where the loaded rows carry an objective)
+        f = oracle.linear_fbbt(p, LB, UB, self.inc if math.isfinite(self.inc) and not self.relax
+                               else None)
         status = np.full(nb, 12, dtype=np.int32)
         obj = np.full(nb, math.inf)
         x = np.zeros((nb, p.n))
         wo = [None] * nb
         keep = np.nonzero(f.infeas == 0)[0]
-        if keep.size:
+        if self.relax:
+            self._qp_nodes(f, keep, status, obj, x)
+        elif keep.size:
             if self.rel and not self.warm:
                 # the node's optimal basis is needed: dense solve from the root
                 k = keep.size
@@ -221,6 +282,11 @@ class CpuBnbContext:
         decs = [self._decide(f.infeas[i], status[i], obj[i], x[i], ints) for i in range(nb)]
         if self.rel:
             choice = self._rel_round(nodes, decs, obj, x, f, wo)
+        if self.relax:
+            self.max_batch = max(self.max_batch, nb)
+            for i in range(nb):
+                if status[i] == 0:
+                    self._decide_margins(obj[i], x[i], ints, decs[i])
         for i in range(nb):
             dec = decs[i]
             self.tot.ndec[0 if dec == 5 else dec] += 1
@@ -232,6 +298,8 @@ class CpuBnbContext:
                 j, v, up_first = choice[i]
             else:
                 j, v, up_first = self._branch(x[i], ints)
+                if self.relax:
+                    self._branch_margins(x[i], ints, j)
             w = wo[i] if self.warm == 1 else self.ws
             path = wo[i] if self.warm == 2 else None
             if dec == 5:
@@ -250,6 +318,9 @@ class CpuBnbContext:
             down.ub[j] = math.floor(v)
             up = _Node(f.lb[i].copy(), f.ub[i].copy(), obj[i], nodes[i].depth + 1, w, j, v, path)
             up.lb[j] = math.ceil(v)
+            if self.relax:
+                self.nparents += 1
+                down.pid = up.pid = self.nparents
             if self.order == 0:
                 children += [down, up] if up_first else [up, down]   # preferred on top
             else:
@@ -272,6 +343,96 @@ class CpuBnbContext:
         self.tot.last_batch = nb
         self.tot.incumbent = self.inc
         return self.tot
+
+    # -- QP relaxations (bnb.cpp's s.qp, qp_solve_nodes of qp_runtime.cpp) -----
+    def _qp_nodes(self, f, keep, status, obj, x):
+        """The round's node QPs on the boxes K1 left: fills status / obj / x of
+        the nodes ``keep`` (the others stay at 12, skipped, as qp_init leaves
+        them) and the tree's counters.
+
+        lps and pivots in QP mode (bnb_scan_block of bnb.hip counts a node
+        whose final status is not 12 and adds its entry of the iteration
+        array K5 wrote): lps = the nodes that end at 0 (solved) or 2 (an empty
+        box, or rows the phase-1 LP proved infeasible); pivots = K5's
+        iterations of those nodes: the count at convergence, 0 for an empty
+        box, the iteration limit for a node the phase-1 LP settled.  Nodes K1
+        proved infeasible and nodes that end as an engine problem are in
+        neither; the phase-1 LP's own pivots are counted nowhere."""
+        import qp_ipm
+        p, P = self.problem, self.qp
+        self.nskip += len(status) - len(keep)
+        unsettled = []
+        for i in keep:
+            l, u = f.lb[i], f.ub[i]
+            if np.any(l > u):     # qp_init: infeasible before any iteration
+                status[i] = 2
+                self.tot.lps += 1
+                continue
+            key = (l.tobytes(), u.tobytes())
+            r = self.qp_cache.get(key)
+            if r is None:
+                with np.errstate(all='ignore'):   # an infeasible node's iterates overflow
+                    r = qp_ipm.solve_node(P.Q, P.c, P.A, P.b, l, u)
+                # K5 counts the steps it took: all of them at the limit
+                r['iters'] = r['iters'] if r['status'] == 0 else qp_ipm.MAXIT
+                self.qp_cache[key] = r
+            self.ipm.append(dict(lb=l.copy(), ub=u.copy(), status=r['status'],
+                                 obj=r['obj'] + P.k, x=r['x'], iters=r['iters']))
+            if r['status'] == 0:
+                status[i], obj[i], x[i] = 0, r['obj'] + P.k, r['x']
+                self.nsolved += 1
+                self.tot.lps += 1
+                self.tot.pivots += r['iters']
+            else:
+                unsettled.append(i)
+        if unsettled:
+            # no convergence after the iteration limit: the LP min 0 over the
+            # node box on the rows, from the slack basis, decides
+            lst = oracle.dual_simplex(p, f.lb[unsettled], f.ub[unsettled], None)[0]
+            for i, s in zip(unsettled, lst):
+                if s == 2:
+                    status[i] = 2
+                    self.nsettled += 1
+                    self.tot.lps += 1
+                    self.tot.pivots += qp_ipm.MAXIT
+                else:         # a feasible QP the interior point did not solve
+                    status[i] = 12
+                    self.nstatus12 += 1
+
+    def _margin(self, name, v):
+        if v < self.margins[name]:
+            self.margins[name] = float(v)
+
+    def _decide_margins(self, sv, x, ints, dec):
+        """A solved node's distances to the thresholds of its decision: the
+        objective against the two pruning tests, and, where the integrality
+        test ran, each integer column's fractionality against int_tol."""
+        cut = float(self.inc)
+        if math.isfinite(cut):
+            self._margin('prune', abs(sv - (cut - ABS_TOL)))
+            self._margin('prune', abs(sv - (cut - abs(cut) * REL_TOL)))
+        if dec in (0, 3):
+            for j in np.nonzero(ints)[0]:
+                v = float(x[j])
+                self._margin('intg', abs(abs(v - math.floor(v + 0.5)) - INT_TOL))
+
+    def _branch_margins(self, x, ints, bj):
+        """A branching node: the gap between the best and the second-best
+        MaxVio score, and |dd - ud| of the chosen column (the direction)."""
+        sc = []
+        for j in np.nonzero(ints)[0]:
+            v = x[j]
+            if not abs(math.floor(v + 0.5) - v) > INT_TOL:
+                continue
+            dd, ud = v - math.floor(v), math.ceil(v) - v
+            sc.append(0.1 * (0.8 * min(dd, ud) + 0.2 * max(dd, ud)))
+        sc.sort()
+        if len(sc) > 1:
+            self._margin('score', sc[-1] - sc[-2])
+        v = x[bj]
+        self._margin('dir', abs((v - math.floor(v)) - (math.ceil(v) - v)))
+        if math.floor(v) >= 1:
+            self.int_branch += 1
 
     # -- batched reliability branching (bnb_rel.hip) ----------------------------
     def _rel_round(self, nodes, decs, obj, x, f, wo):
