@@ -455,7 +455,8 @@ int mgpu_bnb_config(mgpu_ctx *ctx, int order, int warm);
  *      the interior point does not solve within its iteration limit gets a
  *      phase-1 LP over its box (min 0 s.t. the rows, K3 / K3L): infeasible
  *      rows make it ProvenInfeasible; a feasible one it could not solve ends
- *      the round with MGPU_ERR_ENGINE (decision 4). */
+ *      the round with MGPU_ERR_ENGINE (decision 4).  With mgpu_qp_step_rule
+ *      2 the feasible ones are first solved again with the coupled step. */
 int mgpu_bnb_relaxation(mgpu_ctx *ctx, int kind);
 /* order 2: the reference's own node order — TreeManager's "bfs" NodeHeap
  *          (NodeHeap.cpp:24-47: lowest bound within 1e-6, then shallower,
@@ -873,6 +874,29 @@ int mgpu_qp_solve(mgpu_ctx *ctx, int batch, const double *lb, const double *ub, 
 int mgpu_qp_solve_dev(mgpu_ctx *ctx, int batch, const double *d_lb, const double *d_ub,
                       int maxit, int32_t *d_status, double *d_obj, int32_t *d_iters,
                       double *d_x);
+/* The step rule of K5's corrected step (sticky on the context, default 0;
+ * holds for mgpu_qp_solve[_dev] and for the node QPs of a tree alike):
+ *   0: separate primal and dual step lengths ap, ad (Mehrotra);
+ *   1: one common length min(ap, ad), taken after the fraction to the
+ *      boundary and the cap at 1 (the predictor's two lengths, which enter
+ *      mu_aff, stay separate).  The separate lengths stall on some feasible,
+ *      well-conditioned node QPs (status 6 at any limit) that this rule
+ *      solves in 7 to 21 iterations;
+ *   2: a first pass with rule 0, then the nodes it left at status 6 again
+ *      from the start with rule 1, at the same iteration limit, as a compact
+ *      batch of their own (k nodes: k workgroups per kernel; none: no
+ *      launch).  A retried node carries the second pass's status, obj and x,
+ *      and iters = the limit + the second pass's count: the steps taken.
+ *      mgpu_qp_solve[_dev] retries every status-6 node.  A tree
+ *      (mgpu_bnb_relaxation 1) retries after the phase-1 LP and only the
+ *      nodes whose rows that LP found feasible: infeasible node QPs end at
+ *      status 6 too and are never solved again.  A node the retry solves
+ *      counts once in lps and with limit + count in pivots; one it does not
+ *      solve ends the round with MGPU_ERR_ENGINE as before.
+ * mgpu_qp_retried: the nodes handed to the second pass since the rule was
+ * last set. */
+int mgpu_qp_step_rule(mgpu_ctx *ctx, int rule);
+long long mgpu_qp_retried(mgpu_ctx *ctx);
 /* Diagnostic: which kernels the loaded QP's shape takes per iteration.
  *   flags bit 0   left-looking factor (qp_potrf_ll; 0: qp_potrf)
  *         bit 1   W resident in LDS (qp_trsm_syrk_lds; 0: qp_trsm_syrk)

@@ -24,6 +24,8 @@ struct DevQP {
 
 struct QpWork {
   int B;
+  int rule;                  // launch-uniform step rule of qp_step: 0 separate primal and
+                             // dual step lengths, 1 one common length min(ap, ad)
   const int32_t *skip;       // [B] or null: nonzero = not solved (status 12, obj +inf)
   double *l, *u;             // [B][np] node boxes (padding fixed at 0)
   double *x, *zl, *zu;       // [B][np]
@@ -56,5 +58,17 @@ hipError_t launch_qp_iteration(const DevQP &q, const QpWork &w, hipStream_t s,
                                hipEvent_t *ev = nullptr);
 hipError_t launch_qp_iteration_check(const DevQP &q, const QpWork &w, hipStream_t s);
 hipError_t launch_qp_final(const DevQP &q, const QpWork &w, hipStream_t s);
+
+// The retry's compact batch (mgpu_qp_step_rule 2).  Gather: the nodes b of the
+// round with mask[b] != 0, in their order, into idx[0 .. k), their boxes
+// ([B][n], unpadded) into cl / cu [k][n], and k into *count.  Scatter: the
+// compact batch's results in w (status, obj, iters + it_add, x [k][np]) to the
+// slots idx names of status / obj / iters / x ([B][n], may be null).
+hipError_t launch_qp_retry_gather(const int32_t *mask, int B, int n, const double *lb,
+                                  const double *ub, int32_t *idx, int32_t *count, double *cl,
+                                  double *cu, hipStream_t s);
+hipError_t launch_qp_retry_scatter(const QpWork &w, int k, int n, int np, const int32_t *idx,
+                                   int it_add, int32_t *status, double *obj, int32_t *iters,
+                                   double *x, hipStream_t s);
 
 }  // namespace mgpu

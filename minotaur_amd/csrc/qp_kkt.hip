@@ -952,6 +952,7 @@ __global__ __launch_bounds__(kT) void qp_step(DevQP q, QpWork w) {
   double ap = kQpStep * max_step<J>(s, g, np, 0), ad = kQpStep * max_step<J>(s, g, np, 1);
   ap = fmin(ap, 1.0);
   ad = fmin(ad, 1.0);
+  if (w.rule) ap = ad = fmin(ap, ad);   // rule 1: the coupled step
 #pragma unroll
   for (int k = 0; k < J; ++k) {
     const int j = t + k * kT;
@@ -983,6 +984,69 @@ __global__ __launch_bounds__(kT) void qp_final(DevQP q, QpWork w) {
   f = block_sum(f, red);
   const int st = w.status[b];
   if (t == 0) w.obj[b] = (st == 12 || st == 2) ? INFINITY : f + q.k;
+}
+
+// ---- the retry's compact batch ------------------------------------------------
+// One block per kT nodes of the round.  A block counts the selected nodes
+// before its own (at most B mask words), scans its own kT flags in LDS, and
+// copies the boxes of its selected nodes; the order of the round is kept, so
+// the compact batch is the same on every run.
+__global__ __launch_bounds__(kT) void qp_retry_gather(const int32_t *mask, int B, int n,
+                                                      const double *lb, const double *ub,
+                                                      int32_t *idx, int32_t *count, double *cl,
+                                                      double *cu) {
+  __shared__ int s_scan[kT];
+  __shared__ int s_pos[kT];
+  const int t = threadIdx.x, b0 = blockIdx.x * kT, b = b0 + t;
+  int before = 0;
+  for (int e = t; e < b0; e += kT) before += mask[e] != 0;
+  const int flag = b < B && mask[b] != 0;
+  s_pos[t] = before;
+  s_scan[t] = flag;
+  __syncthreads();
+  for (int o = kT / 2; o > 0; o >>= 1) {   // the count before this block
+    if (t < o) s_pos[t] += s_pos[t + o];
+    __syncthreads();
+  }
+  const int base = s_pos[0];
+  for (int o = 1; o < kT; o <<= 1) {       // inclusive scan of the block's flags
+    const int v = t >= o ? s_scan[t - o] : 0;
+    __syncthreads();
+    s_scan[t] += v;
+    __syncthreads();
+  }
+  const int mine = s_scan[kT - 1];
+  const int at = base + s_scan[t] - flag;
+  __syncthreads();
+  if (flag) {
+    idx[at] = b;
+    s_pos[at - base] = t;
+  }
+  if (b == B - 1) count[0] = base + mine;
+  __syncthreads();
+  for (int i = 0; i < mine; ++i) {
+    const size_t src = (size_t)(b0 + s_pos[i]) * n, dst = (size_t)(base + i) * n;
+    for (int j = t; j < n; j += kT) {
+      cl[dst + j] = lb[src + j];
+      cu[dst + j] = ub[src + j];
+    }
+  }
+}
+
+// one block per node of the compact batch
+__global__ __launch_bounds__(kT) void qp_retry_scatter(QpWork w, int n, int np,
+                                                       const int32_t *idx, int it_add,
+                                                       int32_t *status, double *obj,
+                                                       int32_t *iters, double *x) {
+  const int i = blockIdx.x, t = threadIdx.x;
+  const int b = idx[i];
+  if (t == 0) {
+    status[b] = w.status[i];
+    obj[b] = w.obj[i];
+    iters[b] = it_add + w.iters[i];
+  }
+  if (x != nullptr)
+    for (int j = t; j < n; j += kT) x[(size_t)b * n + j] = w.x[(size_t)i * np + j];
 }
 
 }  // namespace
@@ -1077,6 +1141,22 @@ hipError_t launch_qp_iteration_check(const DevQP &q, const QpWork &w, hipStream_
 
 hipError_t launch_qp_final(const DevQP &q, const QpWork &w, hipStream_t s) {
   hipLaunchKernelGGL(qp_final, dim3(w.B), dim3(kT), sizeof(double) * q.np, s, q, w);
+  return hipGetLastError();
+}
+
+hipError_t launch_qp_retry_gather(const int32_t *mask, int B, int n, const double *lb,
+                                  const double *ub, int32_t *idx, int32_t *count, double *cl,
+                                  double *cu, hipStream_t s) {
+  hipLaunchKernelGGL(qp_retry_gather, dim3((unsigned)((B + kT - 1) / kT)), dim3(kT), 0, s, mask,
+                     B, n, lb, ub, idx, count, cl, cu);
+  return hipGetLastError();
+}
+
+hipError_t launch_qp_retry_scatter(const QpWork &w, int k, int n, int np, const int32_t *idx,
+                                   int it_add, int32_t *status, double *obj, int32_t *iters,
+                                   double *x, hipStream_t s) {
+  hipLaunchKernelGGL(qp_retry_scatter, dim3(k), dim3(kT), 0, s, w, n, np, idx, it_add, status,
+                     obj, iters, x);
   return hipGetLastError();
 }
 

@@ -19,6 +19,7 @@ struct QpState {
   int maxB = 0;
   DevBuf h_l, h_u, h_st, h_obj, h_it, h_x;  // host-path device copies
   DevBuf f_mask, f_st, f_obj, f_it;          // the tree's feasibility LPs
+  DevBuf r_mask, r_idx, r_cnt, r_l, r_u;     // the retry's compact batch (mgpu_qp_step_rule 2)
   std::vector<hipEvent_t> kev;               // mgpu_set_qp_ktime: 4 per iteration
   ~QpState() {
     for (hipEvent_t e : kev) (void)hipEventDestroy(e);
@@ -55,6 +56,13 @@ __global__ void qp_unsettled(const int32_t *st, int B, int32_t *skip) {
   if (b < B) skip[b] = st[b] != 6;
 }
 
+// the retry's nodes: left at the iteration limit and, in a tree, not proven
+// infeasible by their feasibility LP (lst null: no LP ran)
+__global__ void qp_retry_mask(const int32_t *st, const int32_t *lst, int B, int32_t *mask) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b < B) mask[b] = st[b] == 6 && (lst == nullptr || lst[b] != 2);
+}
+
 // their feasibility LP decides: infeasible rows -> ProvenInfeasible; a
 // feasible QP the interior point did not solve -> EngineUnknownStatus
 __global__ void qp_settle(int32_t *st, double *obj, const int32_t *lst, int B) {
@@ -80,6 +88,81 @@ int ensure_qp_batch(mgpu_ctx *c, QpState &s, int B) {
   return MGPU_OK;
 }
 
+// One pass of the interior point over a batch: boxes padded into the
+// workspace, init, the iteration loop, the final residual pass and the
+// objective.  The results stay in the workspace (w.status / obj / iters / x).
+// first: the pass mgpu_last_kernel_ms("qp") starts at and mgpu_set_qp_ktime
+// measures.
+int qp_pass(mgpu_ctx *c, QpState &s, const QpWork &w, const double *lb, const double *ub, int lim,
+            bool first) {
+  const int np = s.dq.np, batch = w.B;
+  const size_t tot = (size_t)batch * np;
+  hipLaunchKernelGGL(pad_boxes, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, c->stream, lb,
+                     ub, s.n, np, batch, w.l, w.u);
+  HIPCHK(c, hipGetLastError());
+  if (first) HIPCHK(c, hipEventRecord(c->ev6, c->stream));
+  HIPCHK(c, launch_qp_init(s.dq, w, c->stream));
+  std::vector<int32_t> hd(batch);
+  const bool ktime = first && c->qp_ktime;
+  if (ktime && s.kev.size() < (size_t)4 * lim) {
+    const size_t have = s.kev.size();
+    s.kev.resize((size_t)4 * lim, nullptr);
+    for (size_t e = have; e < s.kev.size(); ++e) HIPCHK(c, hipEventCreate(&s.kev[e]));
+  }
+  int nit = 0;
+  for (int it = 0; it < lim; ++it) {
+    HIPCHK(c, launch_qp_iteration(s.dq, w, c->stream, ktime ? &s.kev[(size_t)4 * it] : nullptr));
+    nit = it + 1;
+    if (it % 4 == 3) {  // stop once every node has converged
+      HIPCHK(c, hipMemcpyAsync(hd.data(), w.done, (size_t)batch * 4, hipMemcpyDeviceToHost,
+                               c->stream));
+      HIPCHK(c, hipStreamSynchronize(c->stream));
+      bool all = true;
+      for (int b = 0; b < batch && all; ++b) all = hd[b] != 0;
+      if (all) break;
+    }
+  }
+  // a final residual pass marks nodes that converged on the last step
+  HIPCHK(c, launch_qp_iteration_check(s.dq, w, c->stream));
+  HIPCHK(c, launch_qp_final(s.dq, w, c->stream));
+  HIPCHK(c, hipEventRecord(c->ev7, c->stream));
+  if (ktime) {   // per-kernel sums over the iterations (measurement mode)
+    HIPCHK(c, hipEventSynchronize(s.kev[(size_t)4 * nit - 1]));
+    for (int k = 0; k < 3; ++k) c->last_qp_kms[k] = 0.0;
+    for (int it = 0; it < nit; ++it)
+      for (int k = 0; k < 3; ++k) {
+        float ms = 0.f;
+        HIPCHK(c, hipEventElapsedTime(&ms, s.kev[(size_t)4 * it + k], s.kev[(size_t)4 * it + k + 1]));
+        c->last_qp_kms[k] += ms;
+      }
+  }
+  return MGPU_OK;
+}
+
+// mgpu_qp_step_rule 2: the nodes of mask, solved again from the start with
+// the coupled step as a compact batch of their own (K5's kernels launch one
+// workgroup per node: k workgroups, not the round's), and written over their
+// slots of status / obj / iters / x.  No node selected: nothing is launched.
+int qp_retry(mgpu_ctx *c, QpState &s, QpWork w, int batch, const double *lb, const double *ub,
+             int lim, int32_t *status, double *obj, int32_t *iters, double *x) {
+  HIPCHK(c, launch_qp_retry_gather(s.r_mask.as<int32_t>(), batch, s.n, lb, ub,
+                                   s.r_idx.as<int32_t>(), s.r_cnt.as<int32_t>(),
+                                   s.r_l.as<double>(), s.r_u.as<double>(), c->stream));
+  int32_t k = 0;
+  HIPCHK(c, hipMemcpyAsync(&k, s.r_cnt.p, 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (k <= 0) return MGPU_OK;
+  c->qp_retried += k;
+  w.B = k;
+  w.rule = 1;
+  w.skip = nullptr;
+  int rc = qp_pass(c, s, w, s.r_l.as<double>(), s.r_u.as<double>(), lim, false);
+  if (rc != MGPU_OK) return rc;
+  HIPCHK(c, launch_qp_retry_scatter(w, k, s.n, s.dq.np, s.r_idx.as<int32_t>(), lim, status, obj,
+                                    iters, x, c->stream));
+  return MGPU_OK;
+}
+
 }  // namespace
 
 // The batch solve with an optional skip list (the batched tree: nodes its
@@ -92,8 +175,10 @@ int qp_solve_nodes(mgpu_ctx *c, int batch, const double *lb, const double *ub,
   int rc = ensure_qp_batch(c, s, batch);
   if (rc != MGPU_OK) return rc;
   const int np = s.dq.np;
+  const bool retry = c->qp_rule == 2;
   QpWork w{};
   w.B = batch;
+  w.rule = c->qp_rule == 1 ? 1 : 0;
   w.skip = skip;
   w.l = s.l.as<double>();
   w.u = s.u.as<double>();
@@ -111,46 +196,15 @@ int qp_solve_nodes(mgpu_ctx *c, int batch, const double *lb, const double *ub,
   w.iters = s.iters.as<int32_t>();
   w.status = s.status.as<int32_t>();
   w.obj = s.obj.as<double>();
-  const size_t tot = (size_t)batch * np;
-  hipLaunchKernelGGL(pad_boxes, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, c->stream, lb,
-                     ub, s.n, np, batch, w.l, w.u);
-  HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipEventRecord(c->ev6, c->stream));
-  HIPCHK(c, launch_qp_init(s.dq, w, c->stream));
   const int lim = maxit > 0 ? maxit : 80;
-  std::vector<int32_t> hd(batch);
-  if (c->qp_ktime && s.kev.size() < (size_t)4 * lim) {
-    const size_t have = s.kev.size();
-    s.kev.resize((size_t)4 * lim, nullptr);
-    for (size_t e = have; e < s.kev.size(); ++e) HIPCHK(c, hipEventCreate(&s.kev[e]));
+  const unsigned g = (unsigned)((batch + 255) / 256);
+  if (retry) {   // the retry's compact batch: sized with the batch, once
+    for (DevBuf *p : {&s.r_mask, &s.r_idx}) HIPCHK(c, p->ensure((size_t)batch * 4));
+    HIPCHK(c, s.r_cnt.ensure(4));
+    for (DevBuf *p : {&s.r_l, &s.r_u}) HIPCHK(c, p->ensure((size_t)batch * s.n * 8));
   }
-  int nit = 0;
-  for (int it = 0; it < lim; ++it) {
-    HIPCHK(c, launch_qp_iteration(s.dq, w, c->stream, c->qp_ktime ? &s.kev[(size_t)4 * it] : nullptr));
-    nit = it + 1;
-    if (it % 4 == 3) {  // stop once every node has converged
-      HIPCHK(c, hipMemcpyAsync(hd.data(), w.done, (size_t)batch * 4, hipMemcpyDeviceToHost,
-                               c->stream));
-      HIPCHK(c, hipStreamSynchronize(c->stream));
-      bool all = true;
-      for (int b = 0; b < batch && all; ++b) all = hd[b] != 0;
-      if (all) break;
-    }
-  }
-  // a final residual pass marks nodes that converged on the last step
-  HIPCHK(c, launch_qp_iteration_check(s.dq, w, c->stream));
-  HIPCHK(c, launch_qp_final(s.dq, w, c->stream));
-  HIPCHK(c, hipEventRecord(c->ev7, c->stream));
-  if (c->qp_ktime) {   // per-kernel sums over the iterations (measurement mode)
-    HIPCHK(c, hipEventSynchronize(s.kev[(size_t)4 * nit - 1]));
-    for (int k = 0; k < 3; ++k) c->last_qp_kms[k] = 0.0;
-    for (int it = 0; it < nit; ++it)
-      for (int k = 0; k < 3; ++k) {
-        float ms = 0.f;
-        HIPCHK(c, hipEventElapsedTime(&ms, s.kev[(size_t)4 * it + k], s.kev[(size_t)4 * it + k + 1]));
-        c->last_qp_kms[k] += ms;
-      }
-  }
+  rc = qp_pass(c, s, w, lb, ub, lim, true);
+  if (rc != MGPU_OK) return rc;
   HIPCHK(c, hipMemcpyAsync(status, w.status, (size_t)batch * 4, hipMemcpyDeviceToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(obj, w.obj, (size_t)batch * 8, hipMemcpyDeviceToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(iters, w.iters, (size_t)batch * 4, hipMemcpyDeviceToDevice, c->stream));
@@ -160,26 +214,41 @@ int qp_solve_nodes(mgpu_ctx *c, int batch, const double *lb, const double *ub,
                        s.n, np, batch, x);
     HIPCHK(c, hipGetLastError());
   }
-  if (skip != nullptr) {
-    // the batched tree: a node QP still unsettled after the iteration limit
-    // (no convergence, no Farkas ray) gets a phase-1 answer from the loaded
-    // rows: the LP min 0 over the node box (K3 / K3L from the slack basis),
-    // as BQPD's own phase 1 would report an infeasible node QP
-    const unsigned g = (unsigned)((batch + 255) / 256);
-    for (DevBuf *p : {&s.f_mask, &s.f_st, &s.f_it}) HIPCHK(c, p->ensure((size_t)batch * 4));
-    HIPCHK(c, s.f_obj.ensure((size_t)batch * 8));
-    hipLaunchKernelGGL(qp_unsettled, dim3(g), dim3(256), 0, c->stream, status, batch,
-                       s.f_mask.as<int32_t>());
-    HIPCHK(c, hipGetLastError());
-    int rc2 = mgpu_lp_solve_dev(c, batch, lb, ub, s.f_mask.as<int32_t>(), nullptr, nullptr,
-                                nullptr, nullptr, 1, 0, s.f_st.as<int32_t>(),
-                                s.f_obj.as<double>(), s.f_it.as<int32_t>(), nullptr, nullptr,
-                                nullptr, nullptr, nullptr);
-    if (rc2 != MGPU_OK) return rc2;
-    hipLaunchKernelGGL(qp_settle, dim3(g), dim3(256), 0, c->stream, status, obj,
-                       s.f_st.as<int32_t>(), batch);
-    HIPCHK(c, hipGetLastError());
+  if (skip == nullptr) {
+    if (retry) {   // every node the first pass left at its iteration limit
+      hipLaunchKernelGGL(qp_retry_mask, dim3(g), dim3(256), 0, c->stream, status, nullptr, batch,
+                         s.r_mask.as<int32_t>());
+      HIPCHK(c, hipGetLastError());
+      rc = qp_retry(c, s, w, batch, lb, ub, lim, status, obj, iters, x);
+    }
+    return rc;
   }
+  // the batched tree: a node QP still unsettled after the iteration limit
+  // (no convergence, no Farkas ray) gets a phase-1 answer from the loaded
+  // rows: the LP min 0 over the node box (K3 / K3L from the slack basis),
+  // as BQPD's own phase 1 would report an infeasible node QP
+  for (DevBuf *p : {&s.f_mask, &s.f_st, &s.f_it}) HIPCHK(c, p->ensure((size_t)batch * 4));
+  HIPCHK(c, s.f_obj.ensure((size_t)batch * 8));
+  hipLaunchKernelGGL(qp_unsettled, dim3(g), dim3(256), 0, c->stream, status, batch,
+                     s.f_mask.as<int32_t>());
+  HIPCHK(c, hipGetLastError());
+  int rc2 = mgpu_lp_solve_dev(c, batch, lb, ub, s.f_mask.as<int32_t>(), nullptr, nullptr,
+                              nullptr, nullptr, 1, 0, s.f_st.as<int32_t>(),
+                              s.f_obj.as<double>(), s.f_it.as<int32_t>(), nullptr, nullptr,
+                              nullptr, nullptr, nullptr);
+  if (rc2 != MGPU_OK) return rc2;
+  if (retry) {
+    // the retry comes after the LP: an infeasible node QP ends at status 6 as
+    // well (up to a third of a tree's nodes) and must not be solved again
+    hipLaunchKernelGGL(qp_retry_mask, dim3(g), dim3(256), 0, c->stream, status,
+                       s.f_st.as<int32_t>(), batch, s.r_mask.as<int32_t>());
+    HIPCHK(c, hipGetLastError());
+    rc2 = qp_retry(c, s, w, batch, lb, ub, lim, status, obj, iters, x);
+    if (rc2 != MGPU_OK) return rc2;
+  }
+  hipLaunchKernelGGL(qp_settle, dim3(g), dim3(256), 0, c->stream, status, obj,
+                     s.f_st.as<int32_t>(), batch);
+  HIPCHK(c, hipGetLastError());
   return MGPU_OK;
 }
 
@@ -241,6 +310,17 @@ int mgpu_load_qp(mgpu_ctx *c, int n, int m, const double *Q, const double *cvec,
   d.td = 1e-9 * (1.0 + cmax);
   return MGPU_OK;
 }
+
+int mgpu_qp_step_rule(mgpu_ctx *c, int rule) {
+  if (!c) return MGPU_ERR_ARG;
+  if (rule < 0 || rule > 2)
+    return fail(c, MGPU_ERR_ARG, "mgpu_qp_step_rule: 0 (separate), 1 (coupled) or 2 (retry)");
+  c->qp_rule = rule;
+  c->qp_retried = 0;
+  return MGPU_OK;
+}
+
+long long mgpu_qp_retried(mgpu_ctx *c) { return c ? c->qp_retried : 0; }
 
 int mgpu_qp_plan(mgpu_ctx *c, int *flags) {
   if (!c) return MGPU_ERR_ARG;

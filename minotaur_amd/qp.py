@@ -170,20 +170,28 @@ def rows_problem(qp: QpProblem):
 
 
 def solve_tree(ctx, qp: QpProblem, batch=1024, capacity=None, max_rounds=10**9, order=0,
-               incumbent=float('inf')):
+               incumbent=float('inf'), retry=False):
     """Branch-and-bound over QP relaxations (the batched tree with K5 as its
     node relaxation, mgpu_bnb_relaxation 1): returns (incumbent, x, stats,
     seconds).  QPDRelaxer (examples/QPDRelaxer.cpp:56-126) hands each node's
-    QP to BqpdEngine; here a round's nodes go to K5 in one batch."""
+    QP to BqpdEngine; here a round's nodes go to K5 in one batch.
+
+    retry: a feasible node QP on which K5's separate step lengths stall is
+    solved again with the coupled step (mgpu_qp_step_rule 2) instead of ending
+    the tree as an engine problem; the context's rule is 0 afterwards."""
     from . import bnb
     ctx.load(rows_problem(qp))
     ctx.load_qp(qp)
     ctx.bnb_relaxation(1)
+    if retry:
+        ctx.qp_step_rule(2)
     try:
         return bnb.solve(ctx, batch=batch, capacity=capacity, max_rounds=max_rounds,
                          incumbent=incumbent, order=order, warm=0)
     finally:
         ctx.bnb_relaxation(0)
+        if retry:
+            ctx.qp_step_rule(0)
 
 
 def random_miqp(seed: int, nbin: int = 8, ncont: int = 4, m: int = 2, nint: int = 0,

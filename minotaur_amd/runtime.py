@@ -39,7 +39,7 @@ EXPORTS = [
     'mgpu_bnb_round', 'mgpu_bnb_best', 'mgpu_bnb_shard', 'mgpu_bnb_config', 'mgpu_bnb_export',
     'mgpu_bnb_import', 'mgpu_strong_branch',
     'mgpu_strong_branch_dev', 'mgpu_load_qp', 'mgpu_qp_solve', 'mgpu_qp_solve_dev',
-    'mgpu_qp_plan', 'mgpu_quad_plan',
+    'mgpu_qp_plan', 'mgpu_qp_step_rule', 'mgpu_qp_retried', 'mgpu_quad_plan',
     'mgpu_set_node_rows', 'mgpu_lp_solve_rows', 'mgpu_lp_solve_rows_dev', 'mgpu_bnb_brancher',
     'mgpu_bnb_relaxation',
     'mgpu_lp_refactor', 'mgpu_set_lp_pfi_wide', 'mgpu_lp_pfi_cap', 'mgpu_lp_solve_path',
@@ -192,6 +192,9 @@ def load_library():
     lib.mgpu_qp_solve.argtypes = [_P, _I, _P, _P, _I, _P, _P, _P, _P]
     lib.mgpu_qp_solve_dev.argtypes = [_P, _I, _P, _P, _I, _P, _P, _P, _P]
     lib.mgpu_qp_plan.argtypes = [_P, ctypes.POINTER(_I)]
+    lib.mgpu_qp_step_rule.argtypes = [_P, _I]
+    lib.mgpu_qp_retried.argtypes = [_P]
+    lib.mgpu_qp_retried.restype = ctypes.c_longlong
     lib.mgpu_quad_plan.argtypes = [_P, ctypes.POINTER(_I), ctypes.POINTER(ctypes.c_longlong)]
     lib.mgpu_set_node_rows.argtypes = [_P, _I, _I, _P, _P, _I, _P, _P, _P]
     lib.mgpu_lp_refactor.argtypes = [_P] + [_P] * 7
@@ -893,6 +896,17 @@ class Context:
         f = ctypes.c_int(0)
         self._chk(self.lib.mgpu_qp_plan(self.h, ctypes.byref(f)), 'mgpu_qp_plan')
         return f.value & 1, (f.value >> 1) & 1, 2 << ((f.value >> 2) & 3)
+
+    def qp_step_rule(self, rule):
+        """mgpu_qp_step_rule (sticky): 0 separate primal and dual step lengths,
+        1 the coupled step min(ap, ad), 2 rule 0 and then the status-6 nodes
+        again from the start with rule 1 (in a tree: those the phase-1 LP
+        found feasible)."""
+        self._chk(self.lib.mgpu_qp_step_rule(self.h, int(rule)), 'mgpu_qp_step_rule')
+
+    def qp_retried(self) -> int:
+        """mgpu_qp_retried: nodes handed to the retry since the rule was set."""
+        return int(self.lib.mgpu_qp_retried(self.h))
 
     def qp_solve(self, lb, ub, maxit=0, want_x=True):
         lb = _np(lb, np.float64)
