@@ -850,6 +850,75 @@ int mgpu_glob_best(mgpu_ctx *ctx, double *obj, double *x);
  * on (the order kind 1 would make them in). */
 int mgpu_glob_lp_log(mgpu_ctx *ctx, int cap, int32_t *status, double *value, int32_t *iters);
 
+/* Node-sharded multi-GPU search of the spatial tree (MpiBranchAndBound's
+ * round-robin deal, src/base/MpiBranchAndBound.cpp:142-188), after identical
+ * first rounds on every rank: keeps the open nodes whose index is = rank
+ * (mod world); *kept = nodes left.
+ *   order 0: the index is the stack position from the bottom; the kept nodes
+ *            are compacted to slots 0..k-1 in order, with every per-slot array;
+ *   order 2: the index is the position in ascending node-id order; the kept
+ *            nodes keep their ids and pool slots, the others leave the heap
+ *            and their slots become free.
+ * Under relstronger every rank keeps its own pseudocosts from here on, as
+ * every MPI rank of the reference owns its brancher.  qt 0's "first
+ * presolveNode call" is per context: the context's first round (no node
+ * evaluated yet, tot.nodes == 0), whatever was imported before it. */
+int mgpu_glob_shard(mgpu_ctx *ctx, int rank, int world, int *kept);
+
+/* Bound-aware load balancing of the spatial tree on device rows
+ * (MpiBranchAndBound::LoadBalance_, src/base/MpiBranchAndBound.cpp:78-195:
+ * each rank pops its next 50 P candidates with TreeManager::getCandidate
+ * (:93-105), their bounds are all-gathered (:107), sorted (:111-135) and the
+ * i-th best is dealt to rank i mod P (:142-188), one MPI_Send of a serialised
+ * node per move).  A glob node is more than its box, so a row carries all a
+ * node's processing reads, every field exact (integers as f64):
+ *     [ lb (nv) | ub (nv) | rows (R) | tan (T) | node bound | depth ]
+ *     warm 1:        + [ has_basis | head (m) | statuses, 16 two-bit codes
+ *                        per f64, ceil((nv + m) / 16) ]
+ *     brancher >= 1: + [ var | isint | act | dd | ud | plb ]   (var -1: none)
+ * rows: the secant / McCormick row state K2 rewrites from; tan: the tangent
+ * slots (T = 2 nsq S); the basis: the parent's optimal one (has_basis 0: the
+ * slot gets none and the node LP starts from the slack basis); the last six:
+ * the branching that made the node, which updateAfterSolve reads on the
+ * receiving rank.  Orders 0 and 2, warm 0 and 1, every brancher, with and
+ * without squares, lin and obbt.
+ *   mgpu_glob_pick:       this rank's next S candidates: their bounds into
+ *                         lbs[0, *got) (host).  Order 0: the stack top,
+ *                         topmost first.  Order 2: the heap's next S under
+ *                         TreeManager::getCandidate's lazy pruning by the
+ *                         incumbent (pruned nodes are gone, as in a round).
+ *                         The picked nodes stay open until exported.
+ *   mgpu_glob_export_dev: removes the picked nodes idx[0, k) (distinct indices
+ *                         into the last pick, host array) and packs them, in
+ *                         that order, into device rows d_rows[k][W]; the
+ *                         depth-first stack closes its gaps in every per-slot
+ *                         array; order 2 frees their slots.
+ *   mgpu_glob_import_dev: the k rows become open nodes in row order.  Order
+ *                         0: pushed in order (the last row ends on top).
+ *                         Order 2: each takes a free slot and the next node
+ *                         id.  MGPU_ERR_NOMEM, the pool untouched, when they
+ *                         do not fit.
+ *   mgpu_glob_row_width:  W for the tree's configuration.
+ *   mgpu_glob_count:      open nodes and pool slots left for imports.
+ *   mgpu_glob_rebalance:  mgpu_bnb_rebalance on the spatial tree's pool, the
+ *                         same arguments and steps (one shared deal): pick,
+ *                         all-gather of bounds and room, mgpu_lb_deal, the
+ *                         overflow check on every rank, export,
+ *                         mgpu_alltoall_rows_dev, import in deal order.  A
+ *                         world of one returns before touching the pool
+ *                         (*npicked 0).  The first call at a given S sizes
+ *                         every workspace for its worst case; later calls at
+ *                         that S allocate nothing.
+ * An exchange makes a number of copies and launches that does not depend on
+ * k. */
+int mgpu_glob_pick(mgpu_ctx *ctx, int S, double *lbs, int *got);
+int mgpu_glob_export_dev(mgpu_ctx *ctx, int k, const int32_t *idx, double *d_rows);
+int mgpu_glob_import_dev(mgpu_ctx *ctx, int k, const double *d_rows);
+int mgpu_glob_row_width(mgpu_ctx *ctx);
+int mgpu_glob_count(mgpu_ctx *ctx, int *open, int *spare);
+int mgpu_glob_rebalance(mgpu_ctx *ctx, int S, double *picked, int *npicked, double *received,
+                        int *nreceived, long long *moved, int *open_after);
+
 /* ---- QP relaxation with an MFMA KKT block (K5) ---------------
  * Replaces BqpdEngine::solve (src/interfaces/BqpdEngine.cpp:449-534) on the
  * QP relaxation QPDRelaxer builds (examples/QPDRelaxer.cpp:56-126):

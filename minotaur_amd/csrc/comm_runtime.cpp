@@ -91,6 +91,142 @@ int new_state(mgpu_ctx *c, int rank, int world) {
   return MGPU_OK;
 }
 
+// One tree pool as LoadBalance_ sees it: the linear tree's (mgpu_bnb_*) or the
+// spatial tree's (mgpu_glob_*).
+struct PoolOps {
+  const char *name;
+  int (*pick)(mgpu_ctx *, int, double *, int *);
+  int (*count)(mgpu_ctx *, int *, int *);
+  int (*width)(mgpu_ctx *);
+  int (*export_dev)(mgpu_ctx *, int, const int32_t *, double *);
+  int (*import_dev)(mgpu_ctx *, int, const double *);
+  int (*reserve)(mgpu_ctx *, int);
+  bool solo_pick;   // a world of one still picks (and reports the bounds)
+};
+
+// One whole LoadBalance_ (:78-195) on a tree pool, the one deal of the code
+// base (mgpu_bnb_rebalance / mgpu_glob_rebalance in include/mgpu.h).
+int rebalance_pool(mgpu_ctx *c, const PoolOps &ops, int S, double *picked, int *npicked,
+                   double *received, int *nreceived, long long *moved, int *open_after) {
+  if (!c) return MGPU_ERR_ARG;
+  if (S < 1) return fail(c, MGPU_ERR_ARG, "%s: S = %d", ops.name, S);
+  const int P = c->comm ? c->comm->world : 1, me = c->comm ? c->comm->rank : 0;
+  std::vector<double> vec((size_t)S + 1, INFINITY);
+  int k = 0, open = 0, spare = 0;
+  int rc = MGPU_OK;
+  // 1. this rank's next S candidates (TreeManager::getCandidate, :93-105); a
+  // world of one reports them (solo_pick) or leaves the pool untouched
+  if (P > 1 || ops.solo_pick) {
+    rc = ops.pick(c, S, vec.data(), &k);
+    if (rc != MGPU_OK) return rc;
+  }
+  rc = ops.count(c, &open, &spare);
+  if (rc != MGPU_OK) return rc;
+  if (picked) std::memcpy(picked, vec.data(), (size_t)k * 8);
+  if (npicked) *npicked = k;
+  if (P == 1) {   // solo: the deal keeps every node where it is
+    if (nreceived) *nreceived = 0;
+    if (moved) *moved = 0;
+    if (open_after) *open_after = open;
+    return MGPU_OK;
+  }
+  vec[(size_t)S] = (double)spare;
+  // every workspace of this exchange at its worst case for S (this rank
+  // sends at most the S nodes it picked and, dealt round-robin, receives at
+  // most S): sized by the first rebalance, never again for the same S
+  const int W = ops.width(c);
+  if (W < 0) return W;
+  {
+    CommState &s = *c->comm;   // P > 1: a communicator is set
+    const size_t rowb = (size_t)W * 8, gat = (size_t)P * (S + 1) * 8;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, s.send_rows.ensure((size_t)S * rowb));
+    HIPCHK(c, s.recv_rows.ensure((size_t)S * rowb));
+    HIPCHK(c, s.ord_rows.ensure((size_t)S * rowb));
+    HIPCHK(c, s.perm.ensure((size_t)S * 4));
+    if (!s.host) {
+      HIPCHK(c, s.dbuf.ensure(gat + (size_t)(S + 1) * 8));
+      rc = ensure_pin(c, s, gat);
+      if (rc != MGPU_OK) return rc;
+    }
+    rc = ops.reserve(c, S);
+    if (rc != MGPU_OK) return rc;
+  }
+  // 2. one all-gather of the bounds and the pool room (:107)
+  std::vector<double> g((size_t)P * (S + 1));
+  rc = mgpu_allgather_f64(c, vec.data(), S + 1, g.data());
+  if (rc != MGPU_OK) return rc;
+  std::vector<double> lbs((size_t)P * S);
+  for (int r = 0; r < P; ++r)
+    std::memcpy(lbs.data() + (size_t)r * S, g.data() + (size_t)r * (S + 1), (size_t)S * 8);
+  // 3. the common deal (:111-188)
+  std::vector<int32_t> owner((size_t)P * S), local((size_t)P * S), recv((size_t)P * S);
+  const int nd = mgpu_lb_deal(P, S, lbs.data(), owner.data(), local.data(), recv.data());
+  std::vector<long long> gain((size_t)P, 0);
+  long long nmoved = 0;
+  for (int i = 0; i < nd; ++i)
+    if (owner[i] != recv[i]) {
+      ++gain[(size_t)recv[i]];
+      --gain[(size_t)owner[i]];
+      ++nmoved;
+    }
+  // 4. a deal that would overflow some pool fails on every rank (same data)
+  for (int r = 0; r < P; ++r)
+    if ((double)gain[(size_t)r] > g[(size_t)r * (S + 1) + S])
+      return fail(c, MGPU_ERR_STATE, "%s: the deal would overflow rank %d's pool "
+                  "(gain %lld, room %.0f)", ops.name, r, gain[(size_t)r], g[(size_t)r * (S + 1) + S]);
+  // 5. the rows this rank sends, grouped by receiver in deal order; the rows it
+  // receives, in deal order, and where each one lands in the exchange buffer
+  std::vector<int32_t> sc((size_t)P, 0), rcnt((size_t)P, 0), idx;
+  std::vector<int> send_at;
+  for (int i = 0; i < nd; ++i)
+    if (owner[i] == me && recv[i] != me) send_at.push_back(i);
+  std::stable_sort(send_at.begin(), send_at.end(),
+                   [&](int a, int b) { return recv[a] < recv[b]; });
+  for (int i : send_at) {
+    idx.push_back(local[i]);
+    ++sc[(size_t)recv[i]];
+  }
+  std::vector<int> got_at;
+  for (int i = 0; i < nd; ++i)
+    if (recv[i] == me && owner[i] != me) {
+      got_at.push_back(i);
+      ++rcnt[(size_t)owner[i]];
+    }
+  std::vector<int32_t> off((size_t)P, 0), perm;
+  for (int r = 1; r < P; ++r) off[(size_t)r] = off[(size_t)r - 1] + rcnt[(size_t)r - 1];
+  for (int i : got_at) perm.push_back(off[(size_t)owner[i]]++);
+  if (received)
+    for (size_t j = 0; j < got_at.size(); ++j) {
+      const int i = got_at[j];
+      received[j] = lbs[(size_t)owner[i] * S + local[i]];
+    }
+  if (nreceived) *nreceived = (int)got_at.size();
+  CommState &s = *c->comm;
+  const size_t rowb = (size_t)W * 8;
+  const int ks = (int)idx.size(), kr = (int)got_at.size();
+  if (ks > S || kr > S)   // the deal hands each rank at most S nodes
+    return fail(c, MGPU_ERR_STATE, "%s: %d sent / %d received > S = %d", ops.name, ks,
+                kr, S);
+  rc = ops.export_dev(c, ks, ks ? idx.data() : nullptr, s.send_rows.as<double>());
+  if (rc != MGPU_OK) return rc;
+  rc = mgpu_alltoall_rows_dev(c, W, s.send_rows.as<double>(), sc.data(), s.recv_rows.as<double>(),
+                              rcnt.data());
+  if (rc != MGPU_OK) return rc;
+  if (kr > 0) {
+    HIPCHK(c, hipMemcpyAsync(s.perm.p, perm.data(), (size_t)kr * 4, hipMemcpyHostToDevice,
+                             c->stream));
+    HIPCHK(c, launch_bnb_gather_rows(s.recv_rows.as<unsigned char>(), s.ord_rows.as<unsigned char>(),
+                                     rowb, s.perm.as<int32_t>(), kr, c->stream));
+    rc = ops.import_dev(c, kr, s.ord_rows.as<double>());
+    if (rc != MGPU_OK) return rc;
+  }
+  HIPCHK(c, hipStreamSynchronize(c->stream));   // perm is pageable and goes out of scope
+  if (moved) *moved = nmoved;
+  if (open_after) *open_after = open - ks + kr;
+  return MGPU_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -291,118 +427,18 @@ int mgpu_lb_deal(int world, int S, const double *lbs, int32_t *owner, int32_t *l
 
 int mgpu_bnb_rebalance(mgpu_ctx *c, int S, double *picked, int *npicked, double *received,
                        int *nreceived, long long *moved, int *open_after) {
-  if (!c) return MGPU_ERR_ARG;
-  if (S < 1) return fail(c, MGPU_ERR_ARG, "mgpu_bnb_rebalance: S = %d", S);
-  const int P = c->comm ? c->comm->world : 1, me = c->comm ? c->comm->rank : 0;
-  // 1. this rank's next S candidates (TreeManager::getCandidate, :93-105)
-  std::vector<double> vec((size_t)S + 1, INFINITY);
-  int k = 0, open = 0, spare = 0;
-  int rc = mgpu_bnb_pick(c, S, vec.data(), &k);
-  if (rc != MGPU_OK) return rc;
-  rc = mgpu_bnb_count(c, &open, &spare);
-  if (rc != MGPU_OK) return rc;
-  if (picked) std::memcpy(picked, vec.data(), (size_t)k * 8);
-  if (npicked) *npicked = k;
-  if (P == 1) {   // solo: the deal keeps every node where it is
-    if (nreceived) *nreceived = 0;
-    if (moved) *moved = 0;
-    if (open_after) *open_after = open;
-    return MGPU_OK;
-  }
-  vec[(size_t)S] = (double)spare;
-  // every workspace of this exchange at its worst case for S (this rank
-  // sends at most the S nodes it picked and, dealt round-robin, receives at
-  // most S): sized by the first rebalance, never again for the same S
-  const int W = mgpu_bnb_row_width(c);
-  if (W < 0) return W;
-  {
-    CommState &s = *c->comm;   // P > 1: a communicator is set
-    const size_t rowb = (size_t)W * 8, gat = (size_t)P * (S + 1) * 8;
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, s.send_rows.ensure((size_t)S * rowb));
-    HIPCHK(c, s.recv_rows.ensure((size_t)S * rowb));
-    HIPCHK(c, s.ord_rows.ensure((size_t)S * rowb));
-    HIPCHK(c, s.perm.ensure((size_t)S * 4));
-    if (!s.host) {
-      HIPCHK(c, s.dbuf.ensure(gat + (size_t)(S + 1) * 8));
-      rc = ensure_pin(c, s, gat);
-      if (rc != MGPU_OK) return rc;
-    }
-    rc = bnb_reserve_migration(c, S);
-    if (rc != MGPU_OK) return rc;
-  }
-  // 2. one all-gather of the bounds and the pool room (:107)
-  std::vector<double> g((size_t)P * (S + 1));
-  rc = mgpu_allgather_f64(c, vec.data(), S + 1, g.data());
-  if (rc != MGPU_OK) return rc;
-  std::vector<double> lbs((size_t)P * S);
-  for (int r = 0; r < P; ++r)
-    std::memcpy(lbs.data() + (size_t)r * S, g.data() + (size_t)r * (S + 1), (size_t)S * 8);
-  // 3. the common deal (:111-188)
-  std::vector<int32_t> owner((size_t)P * S), local((size_t)P * S), recv((size_t)P * S);
-  const int nd = mgpu_lb_deal(P, S, lbs.data(), owner.data(), local.data(), recv.data());
-  std::vector<long long> gain((size_t)P, 0);
-  long long nmoved = 0;
-  for (int i = 0; i < nd; ++i)
-    if (owner[i] != recv[i]) {
-      ++gain[(size_t)recv[i]];
-      --gain[(size_t)owner[i]];
-      ++nmoved;
-    }
-  // 4. a deal that would overflow some pool fails on every rank (same data)
-  for (int r = 0; r < P; ++r)
-    if ((double)gain[(size_t)r] > g[(size_t)r * (S + 1) + S])
-      return fail(c, MGPU_ERR_STATE, "mgpu_bnb_rebalance: the deal would overflow rank %d's pool "
-                  "(gain %lld, room %.0f)", r, gain[(size_t)r], g[(size_t)r * (S + 1) + S]);
-  // 5. the rows this rank sends, grouped by receiver in deal order; the rows it
-  // receives, in deal order, and where each one lands in the exchange buffer
-  std::vector<int32_t> sc((size_t)P, 0), rcnt((size_t)P, 0), idx;
-  std::vector<int> send_at;
-  for (int i = 0; i < nd; ++i)
-    if (owner[i] == me && recv[i] != me) send_at.push_back(i);
-  std::stable_sort(send_at.begin(), send_at.end(),
-                   [&](int a, int b) { return recv[a] < recv[b]; });
-  for (int i : send_at) {
-    idx.push_back(local[i]);
-    ++sc[(size_t)recv[i]];
-  }
-  std::vector<int> got_at;
-  for (int i = 0; i < nd; ++i)
-    if (recv[i] == me && owner[i] != me) {
-      got_at.push_back(i);
-      ++rcnt[(size_t)owner[i]];
-    }
-  std::vector<int32_t> off((size_t)P, 0), perm;
-  for (int r = 1; r < P; ++r) off[(size_t)r] = off[(size_t)r - 1] + rcnt[(size_t)r - 1];
-  for (int i : got_at) perm.push_back(off[(size_t)owner[i]]++);
-  if (received)
-    for (size_t j = 0; j < got_at.size(); ++j) {
-      const int i = got_at[j];
-      received[j] = lbs[(size_t)owner[i] * S + local[i]];
-    }
-  if (nreceived) *nreceived = (int)got_at.size();
-  CommState &s = *c->comm;
-  const size_t rowb = (size_t)W * 8;
-  const int ks = (int)idx.size(), kr = (int)got_at.size();
-  if (ks > S || kr > S)   // the deal hands each rank at most S nodes
-    return fail(c, MGPU_ERR_STATE, "mgpu_bnb_rebalance: %d sent / %d received > S = %d", ks, kr, S);
-  rc = mgpu_bnb_export_dev(c, ks, ks ? idx.data() : nullptr, s.send_rows.as<double>());
-  if (rc != MGPU_OK) return rc;
-  rc = mgpu_alltoall_rows_dev(c, W, s.send_rows.as<double>(), sc.data(), s.recv_rows.as<double>(),
-                              rcnt.data());
-  if (rc != MGPU_OK) return rc;
-  if (kr > 0) {
-    HIPCHK(c, hipMemcpyAsync(s.perm.p, perm.data(), (size_t)kr * 4, hipMemcpyHostToDevice,
-                             c->stream));
-    HIPCHK(c, launch_bnb_gather_rows(s.recv_rows.as<unsigned char>(), s.ord_rows.as<unsigned char>(),
-                                     rowb, s.perm.as<int32_t>(), kr, c->stream));
-    rc = mgpu_bnb_import_dev(c, kr, s.ord_rows.as<double>());
-    if (rc != MGPU_OK) return rc;
-  }
-  HIPCHK(c, hipStreamSynchronize(c->stream));   // perm is pageable and goes out of scope
-  if (moved) *moved = nmoved;
-  if (open_after) *open_after = open - ks + kr;
-  return MGPU_OK;
+  static const PoolOps ops{"mgpu_bnb_rebalance", mgpu_bnb_pick, mgpu_bnb_count,
+                           mgpu_bnb_row_width, mgpu_bnb_export_dev, mgpu_bnb_import_dev,
+                           bnb_reserve_migration, true};
+  return rebalance_pool(c, ops, S, picked, npicked, received, nreceived, moved, open_after);
+}
+
+int mgpu_glob_rebalance(mgpu_ctx *c, int S, double *picked, int *npicked, double *received,
+                        int *nreceived, long long *moved, int *open_after) {
+  static const PoolOps ops{"mgpu_glob_rebalance", mgpu_glob_pick, mgpu_glob_count,
+                           mgpu_glob_row_width, mgpu_glob_export_dev, mgpu_glob_import_dev,
+                           glob_reserve_migration, false};
+  return rebalance_pool(c, ops, S, picked, npicked, received, nreceived, moved, open_after);
 }
 
 }  // extern "C"

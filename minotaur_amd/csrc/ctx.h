@@ -185,6 +185,8 @@ void glob_state_free(mgpu_ctx *c);  // glob_runtime.cpp
 void comm_state_free(mgpu_ctx *c);  // comm_runtime.cpp
 // the pool's migration workspaces for exchanges of up to S rows (bnb.cpp)
 int bnb_reserve_migration(mgpu_ctx *c, int S);
+// the same for the spatial tree's pool (glob_runtime.cpp)
+int glob_reserve_migration(mgpu_ctx *c, int S);
 // a solve's optimal basis out (rows_runtime.cpp lp_solve_rows_wo)
 struct LpWarmOut {
   int32_t *head;

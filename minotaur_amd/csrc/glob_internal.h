@@ -173,6 +173,39 @@ hipError_t launch_rs_masks(const GlobIO &io, const RsIO &rs, hipStream_t stream)
 hipError_t launch_rs_absorb(const GlobIO &io, const RsIO &rs, hipStream_t stream);
 hipError_t launch_rs_children(const GlobIO &io, const RsIO &rs, hipStream_t stream);
 
+// ---- node migration between ranks (glob_migrate.hip) ------------------------
+// One f64 row per node, every field exact (integers as doubles, basis
+// statuses 2 bits each, 16 per double):
+//   [ lb (nv) | ub (nv) | rows (R) | tan (T) | node bound | depth ]
+//   warm 1:        + [ has_basis | head (m) | statuses, ceil((nv + m) / 16) ]
+//   brancher >= 1: + [ var | isint | act | dd | ud | plb ]   (var -1: none)
+constexpr int kMigStage = 8;    // host staging per row: bound, depth, the branching record
+
+struct GlobMigIO {
+  int k, nv, R, T, m, N, W;
+  int warm, br;                 // the row carries a basis / a branching record
+  const int32_t *slots;         // [k] pool slot of row t
+  double *rows;                 // [k][W]
+  double *plb, *pub, *prows, *ptan, *pnlb;
+  int32_t *pdepth;
+  int32_t *pws_head;
+  int8_t *pws_st;
+  uint8_t *pws_ok;
+  // [k][kMigStage] = [bound | depth | var | isint | act | dd | ud | plb]: the
+  // branching records live on the host per pool slot, so glob_pack reads
+  // entries 2..7 from here (one upload per exchange) and glob_unpack writes
+  // all eight (one download: the host's heap needs bound and depth too)
+  double *stage;
+};
+
+inline size_t glob_mig_width(int nv, int R, int T, int m, int warm, int br) {
+  return 2 * (size_t)nv + (size_t)R + (size_t)T + 2 +
+         (warm ? 1 + (size_t)m + ((size_t)nv + (size_t)m + 15) / 16 : 0) + (br ? 6 : 0);
+}
+
+hipError_t launch_glob_mig_pack(const GlobMigIO &io, hipStream_t stream);
+hipError_t launch_glob_mig_unpack(const GlobMigIO &io, hipStream_t stream);
+
 hipError_t launch_glob_round_tail(const GlobIO &io, hipStream_t stream);
 hipError_t launch_glob_decide(const GlobIO &io, hipStream_t stream);
 hipError_t launch_glob_pack(const GlobIO &io, hipStream_t stream);

@@ -33,6 +33,7 @@
 #include <utility>
 #include <vector>
 
+#include "bnb_internal.h"
 #include "ctx.h"
 #include "glob_internal.h"
 #include "node_heap.h"
@@ -55,7 +56,13 @@ struct GlobRoundBufs {
   DevBuf rs_buf;
 };
 
-struct GlobState : GlobRoundBufs {
+// The pool-side workspaces of a migration exchange (glob_reserve_migration
+// sizes them for a pick size S): kept across trees like the round's buffers.
+struct GlobMigBufs {
+  DevBuf mw_slots, mw_ft, mw_tmp, mw_stage;
+};
+
+struct GlobState : GlobRoundBufs, GlobMigBufs {
   int nv = 0, R = 0, S = 0, T = 0, cap = 0, count = 0, maxb = 0;
   // mgpu_glob_config at init: order 0 stack / 2 reference heap (node_heap.h);
   // warm 0 the root basis / 1 the parent's basis; qt 1 tightenQuad_ at every
@@ -86,6 +93,12 @@ struct GlobState : GlobRoundBufs {
   std::vector<double> rs_hpc;
   std::vector<int32_t> rs_htm, rs_hcs;
   NodeHeap tree;                 // order 2: the open nodes, their ids and pool slots
+  // mgpu_glob_pick: the picked nodes in pick order -- order 0 their pool slots
+  // (the stack top, still in place), order 2 the nodes themselves, held out of
+  // the heap with their slots until the export (or any other call) settles them
+  std::vector<int> pick;
+  std::vector<NodeHeap::Node> held;
+  std::vector<double> mw_hstage;     // the host side of GlobMigIO::stage
   DevBuf pws_head, pws_st, pws_ok;                 // per pool slot: the parent's basis
   double inc = INFINITY;
   bool root_ws = false;
@@ -105,6 +118,7 @@ struct GlobState : GlobRoundBufs {
   // the round-sized buffers and the OBBT engine of the context's last tree
   void adopt(GlobState &old) {
     static_cast<GlobRoundBufs &>(*this) = std::move(old);
+    static_cast<GlobMigBufs &>(*this) = std::move(old);
     std::swap(bte, old.bte);
   }
 };
@@ -166,6 +180,14 @@ RsIO rs_carve(const GlobState &s, int B, int m, int N, uintptr_t base, size_t *t
   r.obs = (RsObs *)take((size_t)r.obs_cap * sizeof(RsObs));
   *total = off;
   return r;
+}
+
+// the nodes of the last mgpu_glob_pick that were not exported are open nodes
+// like any other again (order 2: back in the heap under their own ids)
+void glob_settle_pick(GlobState &s) {
+  for (const NodeHeap::Node &n : s.held) s.tree.put_back(n);
+  s.held.clear();
+  s.pick.clear();
 }
 
 int ensure_glob_batch(mgpu_ctx *c, GlobState &s, int B) {
@@ -1022,6 +1044,7 @@ int mgpu_glob_round(mgpu_ctx *c, int batch, double incumbent, mgpu_glob_stats *s
   if (!c->glob) return fail(c, MGPU_ERR_STATE, "mgpu_glob_round: mgpu_glob_init first");
   if (batch < 1) return fail(c, MGPU_ERR_ARG, "mgpu_glob_round: batch < 1");
   GlobState &s = *c->glob;
+  glob_settle_pick(s);
   if (s.brancher == 1) batch = 1;   // relstronger: the reference's node at a time
   const QuadState &q = *c->quad;
   HIPCHK(c, hipSetDevice(c->device));
@@ -1388,6 +1411,344 @@ int mgpu_glob_best(mgpu_ctx *c, double *obj, double *x) {
   if (!c->glob) return fail(c, MGPU_ERR_STATE, "mgpu_glob_best: mgpu_glob_init first");
   if (obj) *obj = c->glob->inc;
   if (x) std::memcpy(x, c->glob->best_x.data(), (size_t)c->glob->nv * 8);
+  return MGPU_OK;
+}
+
+// Node migration for the node-sharded spatial tree (MpiBranchAndBound::
+// LoadBalance_, MpiBranchAndBound.cpp:78-195; the candidates come from
+// TreeManager::getCandidate).  mgpu_glob_pick is the pop (the nodes stay open,
+// only their bounds leave), mgpu_glob_export_dev packs the chosen ones into
+// device rows and removes them, mgpu_glob_import_dev places received rows.
+// The row (glob_migrate.hip; mgpu_glob_row_width) carries everything a node's
+// processing reads: box, row state, tangent slots, bound, depth, the parent's
+// basis (warm 1) and the branching record (relstronger).
+}  // extern "C"
+
+namespace {
+
+// every per-slot device array of the pool
+std::vector<std::pair<DevBuf *, size_t>> glob_slot_rows(GlobState &s, int m) {
+  const size_t nv = (size_t)s.nv, N = nv + (size_t)m;
+  std::vector<std::pair<DevBuf *, size_t>> r = {{&s.plb, nv * 8}, {&s.pub, nv * 8},
+                                                {&s.prows, (size_t)s.R * 8}, {&s.pnlb, 8},
+                                                {&s.pdepth, 4}};
+  if (s.T > 0) r.push_back({&s.ptan, (size_t)s.T * 8});
+  if (s.warm == 1) {
+    r.push_back({&s.pws_head, (size_t)m * 4});
+    r.push_back({&s.pws_st, N});
+    r.push_back({&s.pws_ok, 1});
+  }
+  return r;
+}
+
+size_t glob_width(const mgpu_ctx *c, const GlobState &s) {
+  return glob_mig_width(s.nv, s.R, s.T, c->lp.m, s.warm == 1, s.brancher >= 1);
+}
+
+int glob_open(const GlobState &s) {
+  return s.order == 2 ? s.tree.open() + (int)s.held.size() : s.count;
+}
+
+// the device slot list and the kernels' view of the pool for k rows
+int glob_mig_io(mgpu_ctx *c, GlobState &s, const std::vector<int32_t> &slots, double *rows,
+                GlobMigIO *io) {
+  const int k = (int)slots.size();
+  HIPCHK(c, s.mw_slots.ensure((size_t)k * 4));
+  HIPCHK(c, s.mw_stage.ensure((size_t)k * kMigStage * 8));
+  HIPCHK(c, hipMemcpyAsync(s.mw_slots.p, slots.data(), (size_t)k * 4, hipMemcpyHostToDevice,
+                           c->stream));
+  *io = GlobMigIO{};
+  io->k = k;
+  io->nv = s.nv;
+  io->R = s.R;
+  io->T = s.T;
+  io->m = c->lp.m;
+  io->N = s.nv + c->lp.m;
+  io->W = (int)glob_width(c, s);
+  io->warm = s.warm == 1;
+  io->br = s.brancher >= 1;
+  io->slots = s.mw_slots.as<int32_t>();
+  io->rows = rows;
+  io->plb = s.plb.as<double>();
+  io->pub = s.pub.as<double>();
+  io->prows = s.prows.as<double>();
+  io->ptan = s.T > 0 ? s.ptan.as<double>() : nullptr;
+  io->pnlb = s.pnlb.as<double>();
+  io->pdepth = s.pdepth.as<int32_t>();
+  if (s.warm == 1) {
+    io->pws_head = s.pws_head.as<int32_t>();
+    io->pws_st = s.pws_st.as<int8_t>();
+    io->pws_ok = s.pws_ok.as<uint8_t>();
+  }
+  io->stage = s.mw_stage.as<double>();
+  return MGPU_OK;
+}
+
+// packs the nodes at pool slots `slots` into `buf` (device rows); depth-first:
+// the slots lie in the stack's top `region` slots, the others of that region
+// keep their order and close the gaps, in every per-slot array
+int glob_take_nodes(mgpu_ctx *c, GlobState &s, const std::vector<int32_t> &slots, int region,
+                    double *buf) {
+  const int k = (int)slots.size();
+  if (k == 0) return MGPU_OK;
+  GlobMigIO io;
+  int rc = glob_mig_io(c, s, slots, buf, &io);
+  if (rc != MGPU_OK) return rc;
+  if (s.brancher >= 1) {   // the branching records: one staged copy
+    s.mw_hstage.assign((size_t)k * kMigStage, 0.0);
+    for (int t = 0; t < k; ++t) {
+      const GlobState::BrInfo &bi = s.pinfo[(size_t)slots[(size_t)t]];
+      double *h = s.mw_hstage.data() + (size_t)t * kMigStage;
+      h[2] = (double)bi.var;
+      h[3] = (double)bi.isint;
+      h[4] = bi.act;
+      h[5] = bi.dd;
+      h[6] = bi.ud;
+      h[7] = bi.plb;
+    }
+    HIPCHK(c, hipMemcpyAsync(s.mw_stage.p, s.mw_hstage.data(), (size_t)k * kMigStage * 8,
+                             hipMemcpyHostToDevice, c->stream));
+  }
+  HIPCHK(c, launch_glob_mig_pack(io, c->stream));
+  if (s.order == 0) {
+    const int base = s.count - region;
+    std::vector<uint8_t> gone((size_t)region, 0);
+    for (int32_t v : slots) gone[(size_t)(v - base)] = 1;
+    std::vector<int32_t> ft;   // [from | to]: only rows that change place move
+    std::vector<int32_t> t2;
+    int w = 0;
+    for (int t = 0; t < region; ++t) {
+      if (gone[(size_t)t]) continue;
+      if (t != w) {
+        ft.push_back(base + t);
+        t2.push_back(base + w);
+      }
+      ++w;
+    }
+    if (!ft.empty()) {
+      const int km = (int)ft.size();
+      ft.insert(ft.end(), t2.begin(), t2.end());
+      auto rows = glob_slot_rows(s, c->lp.m);
+      size_t most = 0;
+      for (auto &r : rows) most = r.second > most ? r.second : most;
+      HIPCHK(c, s.mw_ft.ensure((size_t)km * 8));
+      HIPCHK(c, s.mw_tmp.ensure((size_t)km * most));
+      HIPCHK(c, hipMemcpyAsync(s.mw_ft.p, ft.data(), (size_t)km * 8, hipMemcpyHostToDevice,
+                               c->stream));
+      for (auto &r : rows)
+        HIPCHK(c, launch_bnb_move_rows(r.first->as<unsigned char>(), s.mw_tmp.as<unsigned char>(),
+                                       r.second, s.mw_ft.as<int32_t>(),
+                                       s.mw_ft.as<int32_t>() + km, km, c->stream));
+    }
+    s.count -= k;
+  }
+  HIPCHK(c, hipStreamSynchronize(c->stream));   // the staged host arrays go out of scope
+  return MGPU_OK;
+}
+
+// places k device rows as open nodes in row order: on top of the stack, or
+// (order 2) each in a free pool slot under the next node id
+int glob_place_nodes(mgpu_ctx *c, GlobState &s, int k, const double *buf) {
+  if (k == 0) return MGPU_OK;
+  const int room = s.order == 2 ? s.tree.spare() : s.cap - s.count;
+  if (k > room)
+    return fail(c, MGPU_ERR_NOMEM, "mgpu_glob_import_dev: %d rows, the node pool has room for %d",
+                k, room);
+  std::vector<int32_t> slots((size_t)k);
+  for (int t = 0; t < k; ++t)
+    slots[(size_t)t] = s.order == 2 ? s.tree.take_slot() : s.count + t;
+  GlobMigIO io;
+  int rc = glob_mig_io(c, s, slots, const_cast<double *>(buf), &io);
+  if (rc != MGPU_OK) return rc;
+  HIPCHK(c, launch_glob_mig_unpack(io, c->stream));
+  s.mw_hstage.resize((size_t)k * kMigStage);
+  HIPCHK(c, hipMemcpyAsync(s.mw_hstage.data(), s.mw_stage.p, (size_t)k * kMigStage * 8,
+                           hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (s.order == 2) {
+    for (int t = 0; t < k; ++t) {
+      const double *h = s.mw_hstage.data() + (size_t)t * kMigStage;
+      if (s.brancher >= 1) {
+        GlobState::BrInfo bi;
+        bi.var = (int)h[2];
+        bi.isint = (int)h[3];
+        bi.act = h[4];
+        bi.dd = h[5];
+        bi.ud = h[6];
+        bi.plb = h[7];
+        s.pinfo[(size_t)slots[(size_t)t]] = bi;
+      }
+      s.tree.push(h[0], (int)h[1], slots[(size_t)t]);
+    }
+  } else {
+    s.count += k;
+  }
+  return MGPU_OK;
+}
+
+int check_glob(mgpu_ctx *c, const char *what) {
+  if (!c) return MGPU_ERR_ARG;
+  if (!c->glob) return fail(c, MGPU_ERR_STATE, "%s: mgpu_glob_init first", what);
+  return MGPU_OK;
+}
+
+}  // namespace
+
+// The pool-side migration workspaces for an exchange of up to S rows (a pick
+// of S, an export of k <= S of them with the stack's compaction, an import
+// of k <= S): sized once for that worst case (mgpu_glob_rebalance calls this
+// first), so later exchanges at that S allocate nothing.
+int glob_reserve_migration(mgpu_ctx *c, int S) {
+  int rc = check_glob(c, "mgpu_glob_rebalance");
+  if (rc != MGPU_OK) return rc;
+  GlobState &s = *c->glob;
+  const size_t k = (size_t)(S > 0 ? S : 1);
+  size_t most = 0;
+  for (auto &r : glob_slot_rows(s, c->lp.m)) most = r.second > most ? r.second : most;
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, s.mw_slots.ensure(k * 4));
+  HIPCHK(c, s.mw_stage.ensure(k * kMigStage * 8));
+  HIPCHK(c, s.mw_ft.ensure(k * 8));
+  HIPCHK(c, s.mw_tmp.ensure(k * most));
+  return MGPU_OK;
+}
+
+extern "C" {
+
+int mgpu_glob_shard(mgpu_ctx *c, int rank, int world, int *kept) {
+  int rc = check_glob(c, "mgpu_glob_shard");
+  if (rc != MGPU_OK) return rc;
+  if (world < 1 || rank < 0 || rank >= world)
+    return fail(c, MGPU_ERR_ARG, "mgpu_glob_shard: bad rank/world");
+  GlobState &s = *c->glob;
+  HIPCHK(c, hipSetDevice(c->device));
+  glob_settle_pick(s);
+  int k = 0;
+  if (s.order == 2) {
+    k = s.tree.shard(rank, world);
+  } else {
+    // stack position i from the bottom stays when i = rank (mod world): slot
+    // j <- slot rank + j world, for every per-slot array
+    std::vector<int32_t> ft, to;
+    for (int i = rank; i < s.count; i += world, ++k)
+      if (i != k) {
+        ft.push_back(i);
+        to.push_back(k);
+      }
+    if (!ft.empty()) {
+      const int km = (int)ft.size();
+      ft.insert(ft.end(), to.begin(), to.end());
+      auto rows = glob_slot_rows(s, c->lp.m);
+      size_t most = 0;
+      for (auto &r : rows) most = r.second > most ? r.second : most;
+      HIPCHK(c, s.mw_ft.ensure((size_t)km * 8));
+      HIPCHK(c, s.mw_tmp.ensure((size_t)km * most));
+      HIPCHK(c, hipMemcpyAsync(s.mw_ft.p, ft.data(), (size_t)km * 8, hipMemcpyHostToDevice,
+                               c->stream));
+      for (auto &r : rows)
+        HIPCHK(c, launch_bnb_move_rows(r.first->as<unsigned char>(), s.mw_tmp.as<unsigned char>(),
+                                       r.second, s.mw_ft.as<int32_t>(),
+                                       s.mw_ft.as<int32_t>() + km, km, c->stream));
+      HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+  }
+  s.count = k;
+  s.tot.open = k;
+  if (kept) *kept = k;
+  return MGPU_OK;
+}
+
+int mgpu_glob_pick(mgpu_ctx *c, int S, double *lbs, int *got) {
+  int rc = check_glob(c, "mgpu_glob_pick");
+  if (rc != MGPU_OK) return rc;
+  if (S < 0 || (S > 0 && !lbs) || !got)
+    return fail(c, MGPU_ERR_ARG, "mgpu_glob_pick: bad argument");
+  GlobState &s = *c->glob;
+  HIPCHK(c, hipSetDevice(c->device));
+  glob_settle_pick(s);
+  *got = 0;
+  if (s.order == 2) {
+    // TreeManager::getCandidate S times: the heap top, pruned lazily under
+    // the incumbent (the pruned nodes are gone, as in a round)
+    s.held = s.tree.hold(S, s.inc).nodes;
+    for (size_t t = 0; t < s.held.size(); ++t) lbs[t] = s.held[t].lb;
+    *got = (int)s.held.size();
+    s.count = glob_open(s);
+    s.tot.open = s.count;
+    return MGPU_OK;
+  }
+  const int k = S < s.count ? S : s.count;   // the stack's top, topmost first
+  if (k > 0) {
+    std::vector<double> v((size_t)k);
+    HIPCHK(c, hipMemcpyAsync(v.data(), s.pnlb.as<double>() + (s.count - k), (size_t)k * 8,
+                             hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (int t = 0; t < k; ++t) {
+      lbs[t] = v[(size_t)(k - 1 - t)];
+      s.pick.push_back(s.count - 1 - t);
+    }
+  }
+  *got = k;
+  return MGPU_OK;
+}
+
+int mgpu_glob_export_dev(mgpu_ctx *c, int k, const int32_t *idx, double *buf) {
+  int rc = check_glob(c, "mgpu_glob_export_dev");
+  if (rc != MGPU_OK) return rc;
+  GlobState &s = *c->glob;
+  if (k < 0 || (k > 0 && (!idx || !buf)))
+    return fail(c, MGPU_ERR_ARG, "mgpu_glob_export_dev: bad argument");
+  const int np = s.order == 2 ? (int)s.held.size() : (int)s.pick.size();
+  std::vector<uint8_t> seen((size_t)(np > 0 ? np : 1), 0);
+  std::vector<int32_t> slots;
+  for (int t = 0; t < k; ++t) {
+    if (idx[t] < 0 || idx[t] >= np || seen[(size_t)idx[t]])
+      return fail(c, MGPU_ERR_ARG, "mgpu_glob_export_dev: index %d is not a distinct entry of "
+                  "the last mgpu_glob_pick (%d nodes)", idx[t], np);
+    seen[(size_t)idx[t]] = 1;
+    slots.push_back(s.order == 2 ? s.held[(size_t)idx[t]].slot : s.pick[(size_t)idx[t]]);
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  rc = glob_take_nodes(c, s, slots, np, buf);
+  if (rc == MGPU_OK && s.order == 2) {   // the exported nodes' slots are free
+    std::vector<NodeHeap::Node> stay;
+    for (int t = 0; t < np; ++t) {
+      if (seen[(size_t)t]) s.tree.drop(s.held[(size_t)t]);
+      else stay.push_back(s.held[(size_t)t]);
+    }
+    s.held.swap(stay);
+  }
+  glob_settle_pick(s);
+  s.count = glob_open(s);
+  s.tot.open = s.count;
+  return rc;
+}
+
+int mgpu_glob_import_dev(mgpu_ctx *c, int k, const double *buf) {
+  int rc = check_glob(c, "mgpu_glob_import_dev");
+  if (rc != MGPU_OK) return rc;
+  if (k < 0 || (k > 0 && !buf)) return fail(c, MGPU_ERR_ARG, "mgpu_glob_import_dev: bad argument");
+  GlobState &s = *c->glob;
+  HIPCHK(c, hipSetDevice(c->device));
+  glob_settle_pick(s);
+  rc = glob_place_nodes(c, s, k, buf);
+  s.count = glob_open(s);
+  s.tot.open = s.count;
+  return rc;
+}
+
+int mgpu_glob_row_width(mgpu_ctx *c) {
+  int rc = check_glob(c, "mgpu_glob_row_width");
+  if (rc != MGPU_OK) return rc;
+  return (int)glob_width(c, *c->glob);
+}
+
+int mgpu_glob_count(mgpu_ctx *c, int *open, int *spare) {
+  int rc = check_glob(c, "mgpu_glob_count");
+  if (rc != MGPU_OK) return rc;
+  const GlobState &s = *c->glob;
+  if (open) *open = glob_open(s);
+  if (spare) *spare = s.order == 2 ? s.tree.spare() : s.cap - s.count;
   return MGPU_OK;
 }
 

@@ -96,6 +96,60 @@ class NodeHeap {
   int open() const { return (int)(heap_.size() + front_.size()); }
   int hw() const { return hw_; }   // pool high-water mark
 
+  // ---- migration between ranks (MpiBranchAndBound::LoadBalance_, :78-195:
+  // mgpu_glob_pick / _export_dev / _import_dev / _shard) ----------------------
+  // LoadBalance_'s pop of the next S candidates (:93-105): getCandidate S
+  // times as take() does it, pruned nodes freed and counted, but the nodes
+  // that come out KEEP their pool slots: each one goes back under its own id
+  // (put_back) or leaves for another rank (drop).  Until then they are not
+  // counted in open().  Requeued nodes are mid-process and stay.
+  Round hold(int S, double inc) {
+    Round r;
+    while ((int)r.nodes.size() < S && !heap_.empty()) {
+      std::pop_heap(heap_.begin(), heap_.end(), greater);
+      const Node top = heap_.back();
+      heap_.pop_back();
+      if (should_prune(top.lb, inc)) {
+        free_.push_back(top.slot);
+        r.pruned += 1;
+      } else {
+        r.nodes.push_back(top);
+      }
+    }
+    return r;
+  }
+
+  // a held node that stays: the same node (bound, depth, id, slot) is open again
+  void put_back(const Node &n) {
+    heap_.push_back(n);
+    std::push_heap(heap_.begin(), heap_.end(), greater);
+  }
+
+  // a held node that left: its slot is free
+  void drop(const Node &n) { free_.push_back(n.slot); }
+
+  // pool slots an import can still take (free ones, then new ones)
+  int spare() const { return cap_ - hw_ + (int)free_.size(); }
+
+  // MpiBranchAndBound's round-robin deal of the shared first rounds'
+  // open nodes (:142-188): of the open nodes in ascending id order, the ones
+  // at positions = rank (mod world) stay, with their ids and slots; the
+  // others leave the heap and their slots become free.  Returns the kept count.
+  int shard(int rank, int world) {
+    std::vector<long long> ids;
+    for (const Node &n : heap_) ids.push_back(n.id);
+    std::sort(ids.begin(), ids.end());
+    std::vector<Node> keep;
+    for (const Node &n : heap_) {
+      const long pos = (long)(std::lower_bound(ids.begin(), ids.end(), n.id) - ids.begin());
+      if (pos % world == rank) keep.push_back(n);
+      else free_.push_back(n.slot);
+    }
+    heap_.swap(keep);
+    std::make_heap(heap_.begin(), heap_.end(), greater);
+    return (int)heap_.size();
+  }
+
  private:
   static bool greater(const Node &a, const Node &b) {
     if (a.lb > b.lb + 1e-6) return true;

@@ -171,7 +171,8 @@ class NativeComm:
     the engine calls back into torch.distributed (gloo) on host buffers (the
     one-GPU rehearsal of N ranks, where RCCL refuses a shared device).  A
     world of one needs no communicator: every collective is the identity.
-    Load balancing is ONE engine call (mgpu_bnb_rebalance)."""
+    Load balancing is ONE engine call (mgpu_bnb_rebalance, or
+    mgpu_glob_rebalance for the spatial tree)."""
 
     def __init__(self, ctx, rank, world, transport='rccl'):
         self.ctx, self.rank, self.world, self.transport = ctx, rank, world, transport
@@ -230,9 +231,12 @@ def make_comm(ctx, rank, world, device=None):
     return NativeComm(ctx, rank, world, mode)
 
 
-def rebalance(ctx, comm, batch=0):
+def rebalance(ctx, comm, batch=0, tree='bnb'):
     """One bound-aware load-balancing step (MpiBranchAndBound::LoadBalance_,
-    :78-195) on the tree pool of ``ctx``:
+    :78-195) on the tree pool of ``ctx``: the linear tree's (``tree='bnb'``,
+    mgpu_bnb_*) or the spatial tree's (``tree='glob'``, mgpu_glob_*: the same
+    steps, rows that carry the node's row state, tangent slots, basis and
+    branching record too):
 
     1. every rank picks its next S candidates (mgpu_bnb_pick) -- the
        reference pops 50 P per rank; a round of the batched tree takes
@@ -252,12 +256,15 @@ def rebalance(ctx, comm, batch=0):
     Returns (this rank's open count afterwards, nodes moved globally, the
     bounds this rank picked, the bounds of the nodes it received in deal
     order)."""
+    if tree not in ('bnb', 'glob'):
+        raise ValueError(f"rebalance: unknown tree {tree!r}")
     P, r = comm.world, comm.rank
     S = max(MIN_NODES_PER_RANK * P, int(batch))
+    pool = lambda name: getattr(ctx, tree + '_' + name)   # noqa: E731
     if isinstance(comm, NativeComm):      # the whole step inside the engine
-        return ctx.bnb_rebalance(S)
-    lbs = ctx.bnb_pick(S)
-    n_open, spare = ctx.bnb_count()
+        return pool('rebalance')(S)
+    lbs = pool('pick')(S)
+    n_open, spare = pool('count')()
     vec = torch.full((S + 1,), float('inf'), dtype=torch.float64)
     vec[:len(lbs)] = torch.from_numpy(lbs)
     vec[S] = float(spare)
@@ -277,16 +284,16 @@ def rebalance(ctx, comm, batch=0):
     got = moved & (recv == r)
     src = owner[got]
     recv_counts = torch.bincount(src, minlength=P).tolist()
-    rows = ctx.bnb_export_rows(idx)
-    width = ctx.bnb_row_width()
+    rows = pool('export_rows')(idx)
+    width = pool('row_width')()
     out = comm.all_to_all_rows(rows, send_counts, recv_counts, width)
     # the all-to-all delivers rows grouped by sender; import them in deal order
     a2a = torch.sort(src, stable=True).indices               # a2a row -> deal position
     inv = torch.empty_like(a2a)
     inv[a2a] = torch.arange(a2a.numel(), device=a2a.device)
     ordered = out[inv.to(out.device)] if out.shape[0] else out
-    ctx.bnb_import_rows(ordered)
+    pool('import_rows')(ordered)
     n_open = n_open - len(idx) + int(ordered.shape[0])
-    nb = 2 * ctx.problem.n   # the node bound's column
-    got_lbs = ordered[:, nb].cpu().numpy() if ordered.shape[0] else np.empty(0)
+    # the received nodes' bounds in deal order, from the all-gathered picks
+    got_lbs = g[:, :S][owner[got], local[got]].cpu().numpy() if ordered.shape[0] else np.empty(0)
     return n_open, int(moved.sum().item()), lbs, got_lbs

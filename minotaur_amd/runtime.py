@@ -52,6 +52,8 @@ EXPORTS = [
     'mgpu_bnb_growth', 'mgpu_set_sb_chain', 'mgpu_glob_brancher', 'mgpu_glob_lp_log',
     'mgpu_node_serialize', 'mgpu_node_deserialize',
     'mgpu_fbbt_masked_dev', 'mgpu_fbbt_cols_dev', 'mgpu_bnb_fbbt_carry',
+    'mgpu_glob_shard', 'mgpu_glob_pick', 'mgpu_glob_export_dev', 'mgpu_glob_import_dev',
+    'mgpu_glob_row_width', 'mgpu_glob_count', 'mgpu_glob_rebalance',
 ]
 
 COMM_ID_BYTES = 128            # MGPU_COMM_ID_BYTES
@@ -183,6 +185,13 @@ def load_library():
     lib.mgpu_glob_init.argtypes = [_P, _I, _D]
     lib.mgpu_glob_round.argtypes = [_P, _I, _D, ctypes.POINTER(GlobStats)]
     lib.mgpu_glob_best.argtypes = [_P, _P, _P]
+    lib.mgpu_glob_shard.argtypes = [_P, _I, _I, _P]
+    lib.mgpu_glob_pick.argtypes = [_P, _I, _P, _P]
+    lib.mgpu_glob_export_dev.argtypes = [_P, _I, _P, _P]
+    lib.mgpu_glob_import_dev.argtypes = [_P, _I, _P]
+    lib.mgpu_glob_row_width.argtypes = [_P]
+    lib.mgpu_glob_count.argtypes = [_P, _P, _P]
+    lib.mgpu_glob_rebalance.argtypes = [_P, _I, _P, _P, _P, _P, _P, _P]
     lib.mgpu_bnb_round.argtypes = [_P, _I, _D, ctypes.POINTER(BnbStats)]
     lib.mgpu_bnb_best.argtypes = [_P, _P, _P]
     lib.mgpu_bnb_shard.argtypes = [_P, _I, _I, _P]
@@ -1148,6 +1157,81 @@ class Context:
         v = ctypes.c_double(0.0)
         self._chk(self.lib.mgpu_glob_best(self.h, ctypes.byref(v), _hp(x)), 'mgpu_glob_best')
         return v.value, x
+
+    # -- the spatial tree across GPUs (mgpu_glob_shard / _pick / ... ) ----------
+    def glob_shard(self, rank, world) -> int:
+        """mgpu_glob_shard: keep the open nodes whose index (order 0: stack
+        position from the bottom; order 2: position in node-id order) is
+        rank (mod world); returns the kept count."""
+        k = ctypes.c_int(0)
+        self._chk(self.lib.mgpu_glob_shard(self.h, int(rank), int(world), ctypes.byref(k)),
+                  'mgpu_glob_shard')
+        return k.value
+
+    def glob_pick(self, S):
+        """mgpu_glob_pick: bounds of this rank's next S candidates (np [got])."""
+        lbs = np.empty(max(int(S), 1))
+        got = ctypes.c_int(0)
+        self._chk(self.lib.mgpu_glob_pick(self.h, int(S), _hp(lbs), ctypes.byref(got)),
+                  'mgpu_glob_pick')
+        return lbs[:got.value].copy()
+
+    def glob_row_width(self) -> int:
+        """mgpu_glob_row_width: f64 per migration row ([lb | ub | rows | tan |
+        bound | depth], warm 1 the parent's basis, relstronger the branching
+        record)."""
+        w = self.lib.mgpu_glob_row_width(self.h)
+        self._chk(w if w < 0 else 0, 'mgpu_glob_row_width')
+        return int(w)
+
+    def glob_export_rows(self, idx):
+        """mgpu_glob_export_dev: the picked nodes idx leave the pool as device
+        rows [k, W] (a torch tensor on this context's device)."""
+        import torch
+        idx = np.ascontiguousarray(idx, dtype=np.int32)
+        k = len(idx)
+        buf = torch.empty((k, self.glob_row_width()), dtype=torch.float64,
+                          device=torch.device('cuda', self.device))
+        self._chk(self.lib.mgpu_glob_export_dev(self.h, k, _hp(idx) if k else None,
+                                                buf.data_ptr() if k else None),
+                  'mgpu_glob_export_dev')
+        return buf
+
+    def glob_import_rows(self, rows):
+        """mgpu_glob_import_dev: rows [k, W] (torch; moved to this device)
+        become open nodes in row order."""
+        import torch
+        k = int(rows.shape[0])
+        if k == 0:
+            return
+        W = self.glob_row_width()
+        if rows.dim() != 2 or int(rows.shape[1]) != W:
+            raise MgpuError(f"glob_import_rows: rows of shape {tuple(rows.shape)}, the pool's "
+                            f"row width is {W} (mgpu_glob_row_width)")
+        buf = rows.to(device=torch.device('cuda', self.device), dtype=torch.float64).contiguous()
+        self._chk(self.lib.mgpu_glob_import_dev(self.h, k, buf.data_ptr()),
+                  'mgpu_glob_import_dev')
+
+    def glob_count(self):
+        """mgpu_glob_count: (open nodes, pool slots left for imports)."""
+        o, v = ctypes.c_int(0), ctypes.c_int(0)
+        self._chk(self.lib.mgpu_glob_count(self.h, ctypes.byref(o), ctypes.byref(v)),
+                  'mgpu_glob_count')
+        return o.value, v.value
+
+    def glob_rebalance(self, S):
+        """mgpu_glob_rebalance: one LoadBalance_ on the spatial tree -> (open
+        afterwards, nodes moved, the bounds this rank offered, the bounds it
+        received in deal order)."""
+        _, w = self.comm_info()
+        picked = np.empty(int(S))
+        got = np.empty(int(S) * w)
+        npk, ngot, op = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
+        mv = ctypes.c_longlong(0)
+        self._chk(self.lib.mgpu_glob_rebalance(self.h, int(S), _hp(picked), ctypes.byref(npk),
+                                               _hp(got), ctypes.byref(ngot), ctypes.byref(mv),
+                                               ctypes.byref(op)), 'mgpu_glob_rebalance')
+        return op.value, int(mv.value), picked[:npk.value].copy(), got[:ngot.value].copy()
 
     def bnb_best(self):
         x = np.empty(self.problem.n)
